@@ -4,7 +4,15 @@ GB/s on ogbn-products at K = 128 (synthetic stand-in with the same n / nnz /
 max degree: OGB data is not reachable offline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py --full ...        # + CPU baseline, side entries, kernel-timed roofline
+    python bench.py --dump-outputs DIR ...   # the last timed step's C as DIR/C.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the steps and prints the line; whatever
+else is measured beside the headline figure (the CPU baseline legs, the
+hot-column / grouped / analysed side entries, BASELINE configs 3 and 5 beside
+the N = 1 line, the event-timed kernel pass behind a CSR line's `roofline`)
+runs with --full.
 
 Workloads (BASELINE.json configs; the default is the metric's own config):
   products_csr       CSR x dense, ogbn-products stand-in, K=128   (metric; config 4 shape at N>1)
@@ -531,9 +539,37 @@ def cpu_baseline(args, K: int) -> dict:
 
 GRAPH = False  # --graph: replay the step as a captured HIP graph (N = 1)
 GRP32_W = 2    # block rows per group of the bs 32 grouped side line (spmm_bsr32_group_analysis_f32)
+DUMP_ROWS = 65536        # --dump-outputs: rows of C kept when C is larger than DUMP_BYTES
+DUMP_BYTES = 48 << 20
 
 
-def timed_loop(step, h, steps, warmup, world, dist, raw=False):
+def dump_outputs(args, rank: int, **arrays) -> None:
+    """--dump-outputs DIR: what the timed path left in its output tensors, as
+    DIR/<name>.npy (float32; rank 0's tensors at N > 1). A tensor above
+    DUMP_BYTES is written as a fixed sample of its leading dimension: DUMP_ROWS
+    indices drawn once from default_rng(0), sorted, so two runs with the same
+    arguments write the same elements."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() * 4 > DUMP_BYTES and t.shape[0] > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], DUMP_ROWS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        if t.numel() * 4 > DUMP_BYTES:  # few, very long rows (a column-major C): a column sample
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[1], DUMP_BYTES // 4 // t.shape[0],
+                                                          replace=False))
+            t = t[:, torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                np.ascontiguousarray(t.float().cpu().numpy()))
+
+
+def timed_loop(step, h, steps, warmup, world, dist, raw=False, kernel_pass=True, after=None):
+    """Warm up, time `steps` calls of step() on the wall clock, call after()
+    (the output dump) and, with kernel_pass, run the steps once more under the
+    handle's per-launch events for the kernel durations (else none: None / [])."""
     import torch
     for _ in range(warmup):
         step()
@@ -556,15 +592,7 @@ def timed_loop(step, h, steps, warmup, world, dist, raw=False):
             g.replay()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        h.set_timing(True)
-        for _ in range(steps):
-            step()
-        torch.cuda.synchronize()
-        h.set_timing(False)
-        kt = h.kernel_times()
-        if raw:
-            return elapsed, kt
-        return elapsed, (float(np.mean(kt)) if kt else float("nan"))
+        return elapsed, _kernel_pass(step, h, steps, raw, kernel_pass, after)
     # The timed region runs without the per-launch event pairs (two event
     # records around every launch cost several microseconds per step, 8 % of an
     # arxiv-sized step); the kernel durations come from an event-timed pass of
@@ -579,6 +607,17 @@ def timed_loop(step, h, steps, warmup, world, dist, raw=False):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    return elapsed, _kernel_pass(step, h, steps, raw, kernel_pass, after)
+
+
+def _kernel_pass(step, h, steps, raw, kernel_pass, after):
+    """The tail of timed_loop: after() on what the timed steps left, then the
+    event-timed pass (the launches' durations, or their mean unless raw)."""
+    import torch
+    if after is not None:
+        after()
+    if not kernel_pass:
+        return [] if raw else None
     h.set_timing(True)
     for _ in range(steps):
         step()
@@ -586,8 +625,8 @@ def timed_loop(step, h, steps, warmup, world, dist, raw=False):
     h.set_timing(False)
     kt = h.kernel_times()
     if raw:
-        return elapsed, kt
-    return elapsed, (float(np.mean(kt)) if kt else float("nan"))
+        return kt
+    return float(np.mean(kt)) if kt else float("nan")
 
 
 def run_csr_weak(args, W, world, rank, dev, dist):
@@ -622,7 +661,8 @@ def run_csr_weak(args, W, world, rank, dev, dist):
     def step():
         ops.csrmm(d_rp, d_ci, d_v, B, m=n, n=K, k=ncols, ldb=K, C=C, ldc=K, handle=h)
 
-    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, world, dist, raw=True)
+    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, world, dist, raw=True,
+                             after=lambda: dump_outputs(args, rank, C=C))
     kms = float(np.sum(kt)) / args.steps if kt else float("nan")
     tot = torch.tensor([nnz], dtype=torch.float64, device=dev)
     dist.all_reduce(tot)
@@ -724,6 +764,7 @@ def run_csr(args, W, world, rank, dev, dist):
 
         def step():
             sdist.chunked_spmm(shard, C_full, compute_chunk, nch)
+        C_out = C_full
 
         def exchange_only():
             works = []
@@ -739,6 +780,7 @@ def run_csr(args, W, world, rank, dev, dist):
         def step():
             ops.csrmm(d_rp, d_ci, d_v, Bc, m=n, n=K, k=n, ldb=n, order_b=ops.ORDER_COL, C=Cc,
                       ldc=n, order_c=ops.ORDER_COL, handle=h)
+        C_out = Cc
     else:
         C_slot = torch.empty((n, K), device=dev)
         product, ci_step = ops.csrmm, d_ci
@@ -748,17 +790,30 @@ def run_csr(args, W, world, rank, dev, dist):
         def step():
             product(d_rp, ci_step, d_v, B, m=shard.rows, n=K, k=n, ldb=K, C=C_slot, ldc=K,
                     handle=h)
+        C_out = C_slot
 
-    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, world, dist, raw=True)
+    # the event-timed pass (kernel_ms and the byte rates of `roofline`) is a run of
+    # its own: with --full, and in a torch.distributed launch, whose line reports
+    # compute and collective apart
+    kpass = bool(args.full or dist.is_initialized())
+    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, world, dist, raw=True,
+                             kernel_pass=kpass,
+                             after=lambda: dump_outputs(args, rank, C=C_out))
     # kernel time per step (all chunks of a step; one launch when unchunked)
     kms = float(np.sum(kt)) / args.steps if kt else float("nan")
     t = torch.tensor([elapsed, kms], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kms_max = float(t[0]), float(t[1])
-    crf = csr_roofline(shard.rows, shard.colind[int(shard.rowptr[0]):], K, kms)
+    if kpass:
+        crf = csr_roofline(shard.rows, shard.colind[int(shard.rowptr[0]):], K, kms)
+    else:
+        crf = {"achieved": None, "frac": None,
+               "algorithmic_bytes_per_launch": csr_bytes(shard.rows, shard.nnz, K),
+               "bytes_model": "SURVEY 8d gather: one B row per nonzero (the kernel-timed "
+                              "pass and its byte rates: --full)"}
     traffic = None
-    if hot and K == W["K"] and nnz == W["nnz"] and world == 1:
+    if kpass and hot and K == W["K"] and nnz == W["nnz"] and world == 1:
         # counter bytes of the hot kernel on this workload's own shape (tools/pmc_bytes.sh)
         traffic = csr_counter_bytes(args.workload)
         if traffic and crf.get("gather_model_GBps"):
@@ -801,7 +856,8 @@ def run_csr(args, W, world, rank, dev, dist):
         roofline={"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", **crf,
                   "traffic": traffic,
                   "kernel": f"csr_mergepath_kernel<{vec}>" + (" (hot-column hints)" if hot else ""),
-                  "kernel_ms": round(kms, 4), "kernel_ms_max_rank": round(kms_max, 4)},
+                  "kernel_ms": round(kms, 4) if kpass else None,
+                  "kernel_ms_max_rank": round(kms_max, 4) if kpass else None},
         gen_seconds=round(t_gen, 2))
     if (not hot and world == 1 and nch == 1 and args.csr_layout != "col"
             and args.workload == "products_csr" and not args.no_hot_side):
@@ -1035,7 +1091,8 @@ def run_bsr(args, W, world, rank, dev, dist):
         def step():
             fn(d_brp, d_bci, d_bv, B, mb=mb, kb=mb, n=K, bs=bs, ldb=K, C=C, ldc=K, handle=h)
 
-    elapsed, kms = timed_loop(step, h, args.steps, args.warmup, 1, dist)
+    elapsed, kms = timed_loop(step, h, args.steps, args.warmup, 1, dist,
+                              after=lambda: dump_outputs(args, rank, C=C))
     # bs 2 / 4 / 8 fp32: which kernel ran (the grouped MFMA stream from 2^20 blocks when its
     # sharing probe keeps the matrix, else the lane-group VALU kernel; spmm_bsr_small_path)
     small_path = h.small_bsr_path() if bs in (2, 4, 8) and dt == "fp32" and not an else None
@@ -1287,6 +1344,7 @@ def bsr_side(args, workload: str, rank, dev, dist) -> dict:
     import torch
     a = copy.copy(args)
     a.workload, a.K, a.dtype, a.group_rows, a.bsr_layout = workload, 0, None, 0, "row"
+    a.dump_outputs = None  # --dump-outputs holds the headline's C only
     r, _ = run_bsr(a, WORKLOADS[workload], 1, rank, dev, dist)
     rf = r["roofline"]
     keys = ("entry", "group_rows", "ms_per_step", "kernel_ms", "analysis_ms_first_call",
@@ -1349,7 +1407,8 @@ def run_hybrid(args, W, world, rank, dev, dist):
     hopt = args.hybrid_options or 0
     if hopt:
         h.set_hybrid_options(hopt)
-    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, 1, dist, raw=True)
+    elapsed, kt = timed_loop(step, h, args.steps, args.warmup, 1, dist, raw=True,
+                             after=lambda: dump_outputs(args, rank, C=C))
     # Launches per step: one when the library fused both parts (bs = 32; by
     # default when the remainder is short per block row), else
     # the BSR kernel, then the CSR kernel (when both parts exist).
@@ -1502,9 +1561,21 @@ def main() -> None:
                     help="PMC-derived HBM bytes per launch (DESIGN.md §7)")
     ap.add_argument("--graph", action="store_true",
                     help="N = 1: time the step as a replayed HIP graph (launch overhead out)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baseline legs, the "
+                         "hot-column, grouped and analysed side entries, the config 3 / config 5 / "
+                         "products bs 32 side lines and, for the CSR workloads, the kernel-timed "
+                         "pass behind `roofline` (the --no-* options drop single parts of it); "
+                         "without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the C they left as DIR/C.npy (float32; a "
+                         "fixed row sample of a C above 48 MiB)")
     args = ap.parse_args()
     global GRAPH
     GRAPH = args.graph
+    if not args.full:
+        args.no_cpu_baseline = args.no_hot_side = args.no_bsr_sides = True
+        args.no_analysed_side = True
     if args.cpu_baseline_child:
         args.workload = args.workload or "products_csr"
         cpu_baseline_child(args)

@@ -12,7 +12,7 @@ for v in ${VARS:-$(ls spmm-denseblock_amd/lib_var | sed 's/\.so$//')}; do
   echo "$v tests: $(tail -1 $O/pytest_$v.log)"
   [ $rc -ge 124 ] && { cp $O/release.so $L/libspmm_hip.so; exit $rc; }
   for w in ${WLS:-reddit_bsr32 reddit_rcm_bsr32 products_bsr32}; do
-    timeout -k 10 200 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-analysed-side > $O/bw_${v}_$w.log 2>&1; rc=$?
+    timeout -k 10 200 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-analysed-side > $O/bw_${v}_$w.log 2>&1; rc=$?
     grep "^{" $O/bw_${v}_$w.log | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); f=r['roofline']; print('$v', '$w', r['ms_per_step'], f.get('kernel_ms'), f.get('mfma_frac'))"
     [ $rc -ge 124 ] && { cp $O/release.so $L/libspmm_hip.so; exit $rc; }
   done

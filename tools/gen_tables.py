@@ -4,7 +4,7 @@
     python tools/gen_tables.py profiles/r06_final            # print the tables
     python tools/gen_tables.py profiles/r06_final --write    # rewrite the marked blocks
 
-Reads the pass's `bench.log` (the default bench line: the headline with its BASELINE config
+Reads the pass's `bench.log` (the `bench.py --full` line: the headline with its BASELINE config
 3 / config 5 / products bs 32 side entries and the CPU baseline) and `workloads.jsonl` (one
 bench line per workload), and replaces everything between `<!-- numbers:NAME:begin -->` and
 `<!-- numbers:NAME:end -->` in README.md (NAME = headline, workloads, sweep) and INTEGRATION.md
@@ -116,7 +116,7 @@ def load(pass_dir: str):
 def headline_table(h: dict, src: str) -> str:
     rf = h["roofline"]
     cpu = h.get("cpu_baseline") or {}
-    out = [f"From `{src}/bench.log` (the driver's default `python bench.py` line, one MI355X):", "",
+    out = [f"From `{src}/bench.log` (the `python bench.py --full` line, one MI355X):", "",
            "| Line | ms / step | kernel ms | GFLOP/s | roofline | counter bytes | MFMA executed |",
            "|---|---|---|---|---|---|---|"]
     tr = rf.get("traffic")
@@ -157,7 +157,7 @@ def headline_table(h: dict, src: str) -> str:
 
 
 def workloads_table(lines: dict, src: str) -> str:
-    out = [f"From `{src}/workloads.jsonl` (`bench.py --workload W`, 20 steps after 5 warm-up, one MI355X):",
+    out = [f"From `{src}/workloads.jsonl` (`bench.py --full --workload W`, 20 steps after 5 warm-up, one MI355X):",
            "", "| Workload | ms / step | kernel ms | GFLOP/s (2 nnz K / t) | roofline (compulsory bytes) "
            "| counter GB / launch | fp32 or fp16 MFMA executed | analysis ms once | CSR on the same matrix, ms |",
            "|---|---|---|---|---|---|---|---|---|"]

@@ -20,18 +20,18 @@ echo "== gpu suite"
 timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1; rc=$?; tail -2 $O/pytest_gpu.log; stop $rc
 grep -E "FAILED|Error" $O/pytest_gpu.log | head -20
 echo "== smoke"; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; tail -1 $O/smoke.log; stop $rc
-echo "== bench"; timeout -k 10 600 python bench.py > $O/bench.log 2>&1; rc=$?; grep '^{' $O/bench.log | cut -c1-300; stop $rc
+echo "== bench"; timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1; rc=$?; grep '^{' $O/bench.log | cut -c1-300; stop $rc
 echo "== kernel trace"
-(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline) > $O/bench_under_rocprof.log 2>&1; rc=$?; grep '^{' $O/bench_under_rocprof.log | cut -c1-200; stop $rc
+(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline) > $O/bench_under_rocprof.log 2>&1; rc=$?; grep '^{' $O/bench_under_rocprof.log | cut -c1-200; stop $rc
 echo "== N > 1 path at world 1 (torch.distributed.run, 4 chunks, RCCL)"
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29613 bench.py --gpus 1 --workload products_csr_k256 --chunks 4 --steps 10 --warmup 3 > $O/dist_world1.log 2>&1; rc=$?; grep '^{' $O/dist_world1.log | cut -c1-300; stop $rc
 echo "== --gpus 2 on one GPU (must exit 2, no line)"
-timeout -k 10 120 python bench.py --gpus 2 > $O/gpus2.log 2>&1; echo "rc=$?" >> $O/gpus2.log; tail -2 $O/gpus2.log
+timeout -k 10 120 python bench.py --full --gpus 2 > $O/gpus2.log 2>&1; echo "rc=$?" >> $O/gpus2.log; tail -2 $O/gpus2.log
 fi
 if [[ $PH == *b* ]]; then
 : > $O/workloads.jsonl
 for w in ${WLS:-arxiv_csr products_csr_k256 products_csr_hot $BSR_WLS reddit_bsr4_rb32 reddit_bsr2_rb32}; do
-  timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/bw.log 2>&1; rc=$?; stop $rc
+  timeout -k 10 300 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/bw.log 2>&1; rc=$?; stop $rc
   [ $rc -eq 0 ] || { tail -5 $O/bw.log; continue; }
   grep '^{' $O/bw.log >> $O/workloads.jsonl
   grep '^{' $O/bw.log | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); f=r['roofline']; print('$w', r['ms_per_step'], f.get('kernel_ms'), 'frac', f.get('frac'), 'mfma', f.get('mfma_frac'), 'traffic', f.get('traffic'))"

@@ -15,6 +15,6 @@ for l in open('$O/sweep.jsonl'):
     r=json.loads(l); print(r['p'], r['bs'], r['dim'], r['transB'], r['ms'], r['fp32_frac'])"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/tools/ref_sweep.py --densities 0.02 --bs 32,64 --dims 64,128 --transB 1 --skip-csr --reps 3) > $O/kt.log 2>&1; rc=$?; stop $rc
 for w in reddit_bsr32 products_bsr32 reddit_bsr64; do
-  timeout -k 10 200 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-analysed-side > $O/bw_$w.log 2>&1; rc=$?; stop $rc
+  timeout -k 10 200 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-analysed-side > $O/bw_$w.log 2>&1; rc=$?; stop $rc
   grep "^{" $O/bw_$w.log | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); f=r['roofline']; print('$w', r['ms_per_step'], f.get('kernel_ms'), f.get('mfma_frac'))"
 done

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_bsr.py -q -x --timeout 120 
 fi
 for w in ${WLS:-reddit_bsr32_grp products_bsr32_grp products_bsr16_f16_grp}; do
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$w -o kt --output-format csv \
-     -- python3 $R/bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline) > $O/$w.log 2>&1
+     -- python3 $R/bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline) > $O/$w.log 2>&1
   rc=$?; stop $rc
   grep '^{' $O/$w.log | python3 -c "import json,sys; r=json.loads(sys.stdin.read()); print('$w', 'ms', r['ms_per_step'], 'analysis_ms', r.get('analysis_ms'))"
   f=$(find $O/kt_$w -name "*kernel_stats.csv" | head -1)

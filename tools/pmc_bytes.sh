@@ -15,9 +15,9 @@ fi
 for wl in ${WLS:-reddit_bsr32 products_bsr32 products_bsr16_f16}; do
   echo "== $wl"
   BA="--workload $wl --no-cpu-baseline ${BENCH_EXTRA:-}"
-  run kt_$wl rocprofv3 --kernel-trace --stats -d $O/kt_$wl -o kt --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 $BA
+  run kt_$wl rocprofv3 --kernel-trace --stats -d $O/kt_$wl -o kt --output-format csv -- python3 $R/bench.py --full --steps 10 --warmup 3 $BA
   grep '^{' $O/kt_$wl.log | cut -c1-160
-  run fetch_$wl rocprofv3 --pmc FETCH_SIZE -d $O/fetch_$wl -o fetch --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 $BA
-  run write_$wl rocprofv3 --pmc WRITE_SIZE -d $O/write_$wl -o write --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 $BA
+  run fetch_$wl rocprofv3 --pmc FETCH_SIZE -d $O/fetch_$wl -o fetch --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 $BA
+  run write_$wl rocprofv3 --pmc WRITE_SIZE -d $O/write_$wl -o write --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 $BA
 done
 python3 tools/bytes_summary.py $O ${WLS:-reddit_bsr32 products_bsr32 products_bsr16_f16} > $O/bytes.jsonl && cat $O/bytes.jsonl
