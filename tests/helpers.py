@@ -205,17 +205,113 @@ def oracle_divide(L, n, bs, density, rowptr, colind, val):
 
 
 def assert_normwise(got, ref64, absdot, tol, what=""):
-    """|got - ref| <= tol * absdot + 1e-30 elementwise (float64 comparison)."""
+    """|got - ref| <= tol * absdot + 1e-30 elementwise (float64 comparison). A NaN or
+    an infinity in got where the reference is finite is outside it (`err > bound` alone
+    is False for a NaN error and would let an all-NaN result pass)."""
     got = np.asarray(got, np.float64)
-    err = np.abs(got - ref64)
-    bound = tol * absdot + 1e-30
-    bad = err > bound
+    ref64, absdot = np.asarray(ref64, np.float64), np.asarray(absdot, np.float64)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - ref64)
+        bound = tol * absdot + 1e-30
+        bad = (err > bound) | (np.isfinite(ref64) & np.isfinite(bound) & ~(err <= bound))
     if bad.any():
-        i = np.argmax(err - bound)
+        i = np.flatnonzero(bad)[np.argmax(np.nan_to_num((err - bound).ravel()[bad.ravel()],
+                                                        nan=np.inf, posinf=np.inf))]
         raise AssertionError(
             f"{what}: {int(bad.sum())} / {bad.size} elements outside the norm-wise tolerance "
             f"{tol}; worst flat index {i}: got {got.flat[i]!r} ref {ref64.flat[i]!r} "
             f"|a||b| {absdot.flat[i]!r}")
+
+
+# ------------------------------------------------------- framed operands
+# Sentinels of the words a kernel must leave alone (or never sum): NaNs with a
+# payload, compared as raw bits. They are signalling NaNs (quiet bit clear): a copy
+# keeps the bits, any arithmetic returns the quiet form, so even an epilogue that
+# reads a padding word and writes back beta * word + 0 (a quiet NaN sentinel would
+# come back unchanged, payload and all) is caught.
+FRAME_GUARD = 256  # elements before and after the matrix (a multiple of 16 bytes in every type)
+_FRAME_BITS = {np.dtype(np.float16): (np.uint16, 0x7C2A),
+               np.dtype(np.float32): (np.uint32, 0x7F80BEEF),
+               np.dtype(np.float64): (np.uint64, 0x7FF00000DEADBEEF)}
+_FRAME_WORD = {2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+
+class FrameChecker:
+    """The checker of framed(): calling it reads the whole buffer back, asserts bit
+    for bit that every sentinel word (front guard, offset gap, padding columns, back
+    guard) still holds the sentinel and returns the rows x cols data region;
+    unchanged() asserts that the data region kept its bits too (an input operand)."""
+
+    def __init__(self, buffer, host, rows, cols, ld, off, guard):
+        self.buffer, self.host = buffer, host
+        self.rows, self.cols, self.ld, self.off, self.guard = rows, cols, ld, off, guard
+        self.start = guard + off
+        self.word = _FRAME_WORD[host.dtype.itemsize]
+
+    def _read(self):
+        return self.buffer.cpu().numpy()
+
+    def _fail(self, what, region, where, got, want):
+        raise AssertionError(f"{what}: {region} changed, first at {where}: "
+                             f"{int(got):#x}, was {int(want):#x}")
+
+    def __call__(self, what="", _got=None):
+        got = self._read() if _got is None else _got
+        g, h = got.view(self.word), self.host.view(self.word)
+        body0, body1 = self.start, self.start + self.rows * self.ld
+        for region, a, b in (("front guard", 0, self.guard), ("offset gap", self.guard, body0),
+                             ("back guard", body1, g.size)):
+            bad = np.flatnonzero(g[a:b] != h[a:b])
+            if bad.size:
+                self._fail(what, region, f"index {int(bad[0])} of {b - a}", g[a + bad[0]],
+                           h[a + bad[0]])
+        gb = g[body0:body1].reshape(self.rows, self.ld)
+        hb = h[body0:body1].reshape(self.rows, self.ld)
+        bad = np.argwhere(gb[:, self.cols:] != hb[:, self.cols:])
+        if bad.size:
+            r, c = int(bad[0][0]), self.cols + int(bad[0][1])
+            self._fail(what, "padding columns", f"row {r} column {c} (ld {self.ld})", gb[r, c],
+                       hb[r, c])
+        return got[body0:body1].reshape(self.rows, self.ld)[:, :self.cols].copy()
+
+    def unchanged(self, what=""):
+        got = self._read()  # one readback serves both checks
+        self(what, got)
+        g = got.view(self.word)
+        bad = np.flatnonzero(g != self.host.view(self.word))
+        if bad.size:
+            i = int(bad[0]) - self.start
+            self._fail(what, "data region", f"row {i // self.ld} column {i % self.ld}",
+                       g[bad[0]], self.host.view(self.word)[bad[0]])
+
+
+def framed(data2d, ld, off, *, fill=None, device="cuda", guard=FRAME_GUARD):
+    """A rows x cols host array inside a flat buffer on `device`, laid out as
+      [front guard | off elements | rows x ld, the data in columns 0..cols-1 | back guard]
+    with guards of `guard` (>= 256) elements. The off elements, every padding column
+    and both guards hold `fill`: by default the type's sentinel NaN (floating types;
+    integer arrays name their own, e.g. a valid index). Returns (view, checker): the
+    flat tensor that starts at the data (what a caller passes as B or C with leading
+    dimension ld) and its FrameChecker. The view's address modulo 16 is asserted to
+    be what off implies, so a test reaches the alignment it claims."""
+    import torch
+    data2d = np.ascontiguousarray(data2d)
+    rows, cols = data2d.shape
+    dt = data2d.dtype
+    assert ld >= cols and off >= 0 and guard >= FRAME_GUARD and guard * dt.itemsize % 16 == 0
+    host = np.empty(guard + off + rows * ld + guard, dt)
+    if fill is None:
+        word, bits = _FRAME_BITS[dt]
+        host.view(word)[:] = bits
+    else:
+        host[:] = fill
+    start = guard + off
+    host[start:start + rows * ld].reshape(rows, ld)[:, :cols] = data2d
+    buffer = torch.from_numpy(host.copy()).to(device)
+    assert buffer.data_ptr() % 16 == 0, "the allocation itself must be 16-byte aligned"
+    view = buffer[start:]
+    assert view.data_ptr() % 16 == off * dt.itemsize % 16
+    return view, FrameChecker(buffer, host, rows, cols, ld, off, guard)
 
 
 def oracle_reorder(L, kind: str, rowptr, colind, perm=None):
