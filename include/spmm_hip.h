@@ -271,8 +271,15 @@ spmm_status_t spmm_bsrmm_ex_f32(spmm_handle_t handle, spmm_direction_t dir, int 
  *             (NaN and inf count), nnzb words;
  *   valCol    dir = ROW: a column-major copy of the blocks, nnzb * 1024 floats
  *             (may be null for dir = COLUMN, whose blocks already are).
- * Caller-owned buffers. INVALID_VALUE for a bad dir, nnzb < 0, a null
- * pointer that is needed, or a valCol that overlaps bsrVal (the analysis
+ * Caller-owned buffers. bsrVal must be 16-byte aligned (the analysis reads
+ * 16-B vectors). masks and valCol need only their element type's alignment
+ * (4 bytes), here and in spmm_bsrmm_analysed_f32: the analysis writes them one
+ * element at a time. The analysed stream, however, needs a 16-byte aligned
+ * valCol; from any other valCol the product runs the generic kernel (one
+ * element per load, the same result within the fp32 bar, far slower), so a
+ * caller carving valCol out of an arena should place it on 16 bytes.
+ * INVALID_VALUE for a bad dir, nnzb < 0, a null pointer that is needed, a
+ * bsrVal off 16 bytes, or a valCol that overlaps bsrVal (the analysis
  * reads whole blocks while it scatters their columns: no in-place form). */
 spmm_status_t spmm_bsr32_analysis_f32(spmm_handle_t handle, spmm_direction_t dir, int nnzb,
                                       const float* bsrVal, unsigned* masks, float* valCol);
@@ -291,7 +298,10 @@ spmm_status_t spmm_bsrmm_analysed_f32(spmm_handle_t handle, int mb, int kb, int 
                                       int ldc, spmm_order_t orderC);
 
 /* The same analysis for bs = 16 fp16 blocks: masks[k] bit c (c < 16), and for
- * ROW blocks a column-major fp16 copy (nnzb * 256 halves); same checks. */
+ * ROW blocks a column-major fp16 copy (nnzb * 256 halves); same checks, with
+ * bsrVal on 8 bytes. masks (4-byte words) and valCol (2-byte halves) again need
+ * only their element alignment; a valCol off 16 bytes sends
+ * spmm_bsrmm_analysed_f16 to the generic kernel. */
 spmm_status_t spmm_bsr16_analysis_f16(spmm_handle_t handle, spmm_direction_t dir, int nnzb,
                                       const uint16_t* bsrVal, unsigned* masks, uint16_t* valCol);
 
@@ -334,8 +344,11 @@ spmm_status_t spmm_bsrmm_analysed_f16(spmm_handle_t handle, int mb, int kb, int 
  * INVALID_VALUE for a bad dir / groupRows, negative sizes, null pointers that
  * are needed, a row pointer that does not run 0 .. nnzb, a negative block
  * column, block columns not strictly increasing within a block row (sorted,
- * no duplicates, as the csr2bsr output), or a short buffer; NOT_SUPPORTED
- * past 2^31 - 1 items. */
+ * no duplicates, as the csr2bsr output), a short buffer, a bsrVal off 8 bytes
+ * (16 for spmm_bsr32_group_analysis_f32) or a buffer that is not 16-byte
+ * aligned (its sections, at multiples of 256 bytes from its start, are read
+ * and written as 16-byte vectors; the status comes before any launch and the
+ * buffer is not touched); NOT_SUPPORTED past 2^31 - 1 items. */
 spmm_status_t spmm_bsr16_group_analysis_f16(spmm_handle_t handle, spmm_direction_t dir, int mb,
                                             int nnzb, int groupRows, const int* bsrRowPtr,
                                             const int* bsrColInd, const uint16_t* bsrVal,
@@ -360,7 +373,11 @@ spmm_status_t spmm_bsrmm_grouped_f16(spmm_handle_t handle, int mb, int kb, int n
  * block rows share one copy of each B row of their union; unlike bs 16 each
  * block row multiplies only its own nonzero columns (the analysis records them
  * per item), so C is bit-identical to spmm_bsrmm_ex_f32 /
- * spmm_bsrmm_analysed_f32 with the same column-granular non-finite contract.
+ * spmm_bsrmm_analysed_f32 with the same column-granular non-finite contract
+ * (on every block row that those do not split: with a row-major C on a grid of
+ * few block rows they cut a block row far longer than the others into segments
+ * and add the segments' partial sums, which the grouped stream never does;
+ * such a row agrees within the fp32 bar).
  * Same two phases, checks and handle record as spmm_bsr16_group_analysis_f16.
  * The analysis reads A once: for ROW blocks the size query keeps a compact copy
  * of the blocks' nonzero columns in a stream-ordered allocation of 4 KB per block

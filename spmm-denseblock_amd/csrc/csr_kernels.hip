@@ -844,43 +844,26 @@ __global__ __launch_bounds__(kWG) void csr_group_kernel(
 }
 
 // dst (cols x rows, ld_dst) = transpose(src (rows x cols, ld_src)) [+ beta*dst]
-__global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols,
-                                                        const float* __restrict__ src,
-                                                        int ld_src, float* __restrict__ dst,
-                                                        int ld_dst, float beta) {
-  __shared__ float tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int r = r0 + ty + k, c = c0 + tx;
-    if (r < rows && c < cols) tile[ty + k][tx] = src[(size_t)r * ld_src + c];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int c = c0 + ty + k, r = r0 + tx;
-    if (r < rows && c < cols) {
-      float* p = dst + (size_t)c * ld_dst + r;
-      const float x = tile[tx][ty + k];
-      *p = (beta == 0.f) ? x : __builtin_fmaf(beta, *p, x);
-    }
-  }
-}
-
-// The same with 16-byte accesses on both sides (64 x 64 tiles), for any shape:
+// with 16-byte accesses on both sides (64 x 64 tiles), for any shape:
 // loads go along src rows and stores along dst rows as 4-float vectors that
 // need only 4-byte alignment (odd leading dimensions such as the 2,449,029
 // rows of products), scalar at the matrix edges; the tile is read back down
 // its columns (stride 65: conflict-free).
+// FLAT: the tiles of a matrix with more than 65535 tile rows (grid.y's limit; a
+// column-major C from 4,194,241 rows) are numbered along grid.x, column tile
+// fastest as in the 2-D grid; tiles_x is the number of column tiles. Each
+// element's arithmetic is the same in both forms.
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+template <bool FLAT>
 __global__ __launch_bounds__(256) void transpose4_kernel(int rows, int cols,
                                                          const float* __restrict__ src,
                                                          int ld_src, float* __restrict__ dst,
-                                                         int ld_dst, float beta) {
+                                                         int ld_dst, float beta, unsigned tiles_x) {
   __shared__ float tile[64][65];
   const int t = threadIdx.x;
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  const unsigned bx = FLAT ? blockIdx.x % tiles_x : blockIdx.x;
+  const unsigned by = FLAT ? blockIdx.x / tiles_x : blockIdx.y;
+  const int r0 = by * 64, c0 = bx * 64;
   const int q = t & 15, rb = t >> 4;  // 4-float group in a 64-wide row, first row
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -917,37 +900,20 @@ __global__ __launch_bounds__(256) void transpose4_kernel(int rows, int cols,
   }
 }
 
-// 16-bit dst (cols x rows, ld_dst) = transpose(src (rows x cols, ld_src)):
-// the fp16 B operand of the column-major BSR forms, staged row-major.
-__global__ __launch_bounds__(256) void transpose16_kernel(int rows, int cols,
-                                                          const uint16_t* __restrict__ src,
-                                                          int ld_src, uint16_t* __restrict__ dst,
-                                                          int ld_dst) {
-  __shared__ uint16_t tile[32][34];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int r = r0 + ty + k, c = c0 + tx;
-    if (r < rows && c < cols) tile[ty + k][tx] = src[(size_t)r * ld_src + c];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 32; k += 8) {
-    const int c = c0 + ty + k, r = r0 + tx;
-    if (r < rows && c < cols) dst[(size_t)c * ld_dst + r] = tile[tx][ty + k];
-  }
-}
-
-// 16-bit, 64 x 64 tiles, 4 elements (8 B, 2-byte aligned) per access on both sides.
+// 16-bit dst (cols x rows, ld_dst) = transpose(src (rows x cols, ld_src)): the fp16 B
+// operand of the column-major BSR forms, staged row-major. 64 x 64 tiles, 4 elements
+// (8 B, 2-byte aligned) per access on both sides; FLAT as in transpose4_kernel.
 typedef uint16_t u16x4u __attribute__((ext_vector_type(4), aligned(2)));
+template <bool FLAT>
 __global__ __launch_bounds__(256) void transpose16x4_kernel(int rows, int cols,
                                                             const uint16_t* __restrict__ src,
                                                             int ld_src, uint16_t* __restrict__ dst,
-                                                            int ld_dst) {
+                                                            int ld_dst, unsigned tiles_x) {
   __shared__ uint16_t tile[64][66];
   const int t = threadIdx.x;
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  const unsigned bx = FLAT ? blockIdx.x % tiles_x : blockIdx.x;
+  const unsigned by = FLAT ? blockIdx.x / tiles_x : blockIdx.y;
+  const int r0 = by * 64, c0 = bx * 64;
   const int q = t & 15, rb = t >> 4;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -1240,33 +1206,37 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
   return from_hip(hipGetLastError());
 }
 
+// Tile rows beyond grid.y's 65535 go along grid.x (FLAT); past 2^31 - 1 tiles in all
+// there is no launch.
 spmm_status_t launch_transpose(spmm_context* ctx, int rows, int cols, const float* src,
                                int ld_src, float* dst, int ld_dst, float beta) {
   if (rows == 0 || cols == 0) return SPMM_STATUS_SUCCESS;
-  if ((rows + 63) / 64 <= 65535) {
-    dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-    hipLaunchKernelGGL(transpose4_kernel, grid, dim3(256), 0, ctx->stream, rows, cols, src,
-                       ld_src, dst, ld_dst, beta);
+  const unsigned tx = (cols + 63) / 64, ty = (rows + 63) / 64;
+  if (ty <= 65535) {
+    hipLaunchKernelGGL(transpose4_kernel<false>, dim3(tx, ty), dim3(256), 0, ctx->stream, rows,
+                       cols, src, ld_src, dst, ld_dst, beta, tx);
     return from_hip(hipGetLastError());
   }
-  dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-  hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, ctx->stream, rows, cols, src, ld_src,
-                     dst, ld_dst, beta);
+  if ((unsigned long long)tx * ty > 0x7fffffffull) return SPMM_STATUS_NOT_SUPPORTED;
+  hipLaunchKernelGGL(transpose4_kernel<true>, dim3(tx * ty), dim3(256), 0, ctx->stream, rows,
+                     cols, src, ld_src, dst, ld_dst, beta, tx);
   return from_hip(hipGetLastError());
 }
 
+// (src is an array of 16-bit elements, so its address is even: the 4-element accesses'
+// 2-byte alignment always holds and there is no scalar form.)
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst) {
   if (rows == 0 || cols == 0) return SPMM_STATUS_SUCCESS;
-  if ((rows + 63) / 64 <= 65535 && reinterpret_cast<uintptr_t>(src) % 2 == 0) {
-    dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-    hipLaunchKernelGGL(transpose16x4_kernel, grid, dim3(256), 0, ctx->stream, rows, cols, src,
-                       ld_src, dst, ld_dst);
+  const unsigned tx = (cols + 63) / 64, ty = (rows + 63) / 64;
+  if (ty <= 65535) {
+    hipLaunchKernelGGL(transpose16x4_kernel<false>, dim3(tx, ty), dim3(256), 0, ctx->stream, rows,
+                       cols, src, ld_src, dst, ld_dst, tx);
     return from_hip(hipGetLastError());
   }
-  dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-  hipLaunchKernelGGL(transpose16_kernel, grid, dim3(256), 0, ctx->stream, rows, cols, src, ld_src,
-                     dst, ld_dst);
+  if ((unsigned long long)tx * ty > 0x7fffffffull) return SPMM_STATUS_NOT_SUPPORTED;
+  hipLaunchKernelGGL(transpose16x4_kernel<true>, dim3(tx * ty), dim3(256), 0, ctx->stream, rows,
+                     cols, src, ld_src, dst, ld_dst, tx);
   return from_hip(hipGetLastError());
 }
 

@@ -86,6 +86,9 @@ spmm_status_t group_analysis(spmm_handle_t handle, int BS, spmm_direction_t dir,
   // vectors, as spmm_bsr32_analysis_f32 / spmm_bsr16_analysis_f16 require
   if (nnzb > 0 && reinterpret_cast<uintptr_t>(bsrVal) % (BS == 32 ? 16 : 8) != 0)
     return SPMM_STATUS_INVALID_VALUE;
+  // the fill and product kernels read and write the buffer's sections (at multiples of
+  // 256 B from its start) as 16-B vectors
+  if (buffer && reinterpret_cast<uintptr_t>(buffer) % 16 != 0) return SPMM_STATUS_INVALID_VALUE;
   const int E = BS == 16 ? 16 : 8;  // entries per item
   hipStream_t st = handle->stream;
   std::lock_guard<std::mutex> glk(handle->grp_mu);  // the pending record, call to call

@@ -314,6 +314,86 @@ def framed(data2d, ld, off, *, fill=None, device="cuda", guard=FRAME_GUARD):
     return view, FrameChecker(buffer, host, rows, cols, ld, off, guard)
 
 
+# Layouts (off_B, pad_B, off_C, pad_C) in elements that keep every fast path (16-byte
+# bases, ld a multiple of 16 bytes) yet leave the allocation's 256-byte alignment.
+ALIGNED_LAYOUTS_F32 = [(4, 0, 0, 0), (0, 0, 4, 0), (4, 4, 12, 8), (0, 12, 4, 4)]
+# fp16 entries: B's part (off, pad) in halves, a multiple of 8; C (floats) has no
+# requirement there, so each B part goes with every C part.
+ALIGNED_B_F16 = [(8, 0), (8, 8), (0, 16)]
+C_PARTS_F16 = [(0, 0), (4, 8), (1, 0), (0, 1), (3, 1)]
+ALIGNED_LAYOUTS_F16 = [b + c for b in ALIGNED_B_F16 for c in C_PARTS_F16]
+
+# The grouped entries' cases (tests/test_gpu_layout_analysed.py runs them,
+# tests/test_layout_helpers.py checks on the host that each list reaches what it
+# claims): (n, order_b, order_c, (off_B, pad_B, off_C, pad_C)), n = None for "every n
+# of the test". A column-major operand's ld is its row count plus the pad.
+_COL_PARTS_F32 = [(0, 0), (0, 1), (4, 3), (4, 4)]  # 16-byte bases, every pad of 0 / 1 / 3 / 4
+GROUPED_F32_ACCEPTED = (
+    [(None, 0, 0, lay) for lay in [(0, 0, 0, 0), (0, 4, 0, 8)] + ALIGNED_LAYOUTS_F32] +
+    [(None, 1, 0, b + (12, 8)) for b in _COL_PARTS_F32] +
+    [(None, 0, 1, (4, 4) + c) for c in _COL_PARTS_F32] +
+    [(None, 1, 1, b + c) for b, c in zip(_COL_PARTS_F32, reversed(_COL_PARTS_F32))])
+GROUPED_F32_REJECTED = (
+    [(None, 0, 0, lay) for lay in [(0, 1, 0, 0), (0, 2, 0, 0), (0, 0, 0, 1), (0, 0, 0, 2),
+                                   (1, 0, 0, 0), (2, 0, 0, 0), (0, 0, 1, 0), (0, 0, 2, 0)]] +
+    [(None, 1, 0, (1, 0, 0, 0)), (None, 1, 0, (2, 3, 0, 0)), (None, 0, 1, (0, 0, 1, 0)),
+     (None, 0, 1, (0, 0, 2, 1)), (130, 0, 0, (0, 2, 0, 2))])
+GROUPED_F16_ACCEPTED = (
+    [(None, 0, 0, b + c) for b in [(0, 0)] + ALIGNED_B_F16 for c in C_PARTS_F16] +
+    [(None, 0, 1, b + c) for b, c in zip(ALIGNED_B_F16, [c for c in C_PARTS_F16 if c[1]])] +
+    [(None, 1, 0, b + (0, 0)) for b in [(0, 0), (8, 1), (0, 8)]])
+GROUPED_F16_REJECTED = [(None, 0, 0, (0, 1, 0, 0)), (None, 0, 0, (0, 4, 0, 0)),
+                        (None, 0, 0, (1, 0, 0, 0)), (None, 0, 0, (4, 0, 0, 0)),
+                        (132, 0, 0, (0, 4, 0, 0))]
+
+
+# --------------------------------------------------------- BSR test matrices
+def rand_bsr(rng, mb, kb, bs, p, empty_rows=()):
+    rows = []
+    for br in range(mb):
+        cols = np.nonzero(rng.random(kb) < p)[0] if br not in empty_rows else np.zeros(0, int)
+        rows.append(cols)
+    rp = np.concatenate([[0], np.cumsum([len(c) for c in rows])]).astype(np.int32)
+    ci = np.concatenate(rows).astype(np.int32) if rp[-1] else np.zeros(0, np.int32)
+    val = rng.uniform(-1, 1, rp[-1] * bs * bs).astype(np.float32)
+    return rp, ci, val
+
+
+def column_sparse_bsr(rng, mb, kb, bs, p):
+    """BSR whose blocks are mostly empty columns, like csr2bsr output of a
+    sparse graph: per block a random number of active columns (0 = an
+    explicit all-zero block, 1 = a single-column block, up to bs), each
+    active column holding a few nonzeros."""
+    rp, ci, _ = rand_bsr(rng, mb, kb, bs, p, empty_rows=(3,))
+    nnzb = int(rp[-1])
+    v = np.zeros((nnzb, bs, bs), np.float32)
+    for b in range(nnzb):
+        kind = b % 5
+        ncols = {0: 0, 1: 1, 2: 2, 3: bs // 4, 4: bs}[kind]
+        cols = rng.choice(bs, ncols, replace=False)
+        for c in cols:
+            rows = rng.random(bs) < 0.3
+            rows[rng.integers(bs)] = True
+            v[b, rows, c] = rng.uniform(-1, 1, int(rows.sum()))
+    return rp, ci, v.reshape(-1)
+
+
+def long_row_column_sparse_bsr(rng, mb, kb, bs, long_row=5, long_blocks=300):
+    """The matrix of test_bsrmm_analysed / test_bsrmm_analysed_f16 (tests/test_gpu_bsr.py):
+    column_sparse_bsr at fill 0.1 (block row 3 empty), block row `long_row` replaced
+    by `long_blocks` column-sparse blocks (several 64-block chunks, and segments on a
+    shallow grid). fp32 ROW-direction values."""
+    rp, ci, v = column_sparse_bsr(rng, mb, kb, bs, 0.1)
+    rows = [ci[rp[i]:rp[i + 1]] for i in range(mb)]
+    vals = [v.reshape(-1, bs * bs)[rp[i]:rp[i + 1]] for i in range(mb)]
+    rows[long_row] = np.sort(rng.choice(kb, long_blocks, replace=False)).astype(np.int32)
+    _, _, extra = column_sparse_bsr(rng, 1, long_blocks, bs, 1.0)
+    vals[long_row] = extra.reshape(-1, bs * bs)[:long_blocks]
+    rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    ci = np.concatenate(rows).astype(np.int32)
+    return rp, ci, np.concatenate(vals).reshape(-1).astype(np.float32)
+
+
 def oracle_reorder(L, kind: str, rowptr, colind, perm=None):
     """Reordered CSR from the oracle's restatement of reorder_strategy.cc."""
     k = {"degree": 0, "bfs": 1, "rcm": 2, "permute": 3}[kind]

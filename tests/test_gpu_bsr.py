@@ -9,6 +9,8 @@ import pytest
 
 from helpers import (TOL_F16_ACC, TOL_F32, assert_normwise, oracle_bsrmm_f32, oracle_bsrmm_f64,
                      oracle_csrmm_f64)
+from helpers import column_sparse_bsr as _column_sparse_bsr
+from helpers import rand_bsr as _rand_bsr
 
 pytestmark = pytest.mark.gpu
 
@@ -22,17 +24,6 @@ def _ops():
 
 def _dev(*arrs):
     return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrs]
-
-
-def _rand_bsr(rng, mb, kb, bs, p, empty_rows=()):
-    rows = []
-    for br in range(mb):
-        cols = np.nonzero(rng.random(kb) < p)[0] if br not in empty_rows else np.zeros(0, int)
-        rows.append(cols)
-    rp = np.concatenate([[0], np.cumsum([len(c) for c in rows])]).astype(np.int32)
-    ci = np.concatenate(rows).astype(np.int32) if rp[-1] else np.zeros(0, np.int32)
-    val = rng.uniform(-1, 1, rp[-1] * bs * bs).astype(np.float32)
-    return rp, ci, val
 
 
 def test_kat_bsrmm_cu_via_sbsrmm(golden, device):
@@ -586,25 +577,6 @@ def test_lds_staged_kernels(oracle, device, bs, dtype, n, oc):
     tol = TOL_F32 if dtype == "f32" else TOL_F16_ACC
     assert_normwise(got, alpha * ref + beta * C0, abs(alpha) * absd + abs(beta) * np.abs(C0), tol,
                     f"lds bs={bs} {dtype} n={n} oc={oc}")
-
-
-def _column_sparse_bsr(rng, mb, kb, bs, p):
-    """BSR whose blocks are mostly empty columns, like csr2bsr output of a
-    sparse graph: per block a random number of active columns (0 = an
-    explicit all-zero block, 1 = a single-column block, up to bs), each
-    active column holding a few nonzeros."""
-    rp, ci, _ = _rand_bsr(rng, mb, kb, bs, p, empty_rows=(3,))
-    nnzb = int(rp[-1])
-    v = np.zeros((nnzb, bs, bs), np.float32)
-    for b in range(nnzb):
-        kind = b % 5
-        ncols = {0: 0, 1: 1, 2: 2, 3: bs // 4, 4: bs}[kind]
-        cols = rng.choice(bs, ncols, replace=False)
-        for c in cols:
-            rows = rng.random(bs) < 0.3
-            rows[rng.integers(bs)] = True
-            v[b, rows, c] = rng.uniform(-1, 1, int(rows.sum()))
-    return rp, ci, v.reshape(-1)
 
 
 @pytest.mark.parametrize("bs,dtype", [(32, "f32"), (16, "f32"), (16, "f16")])

@@ -429,6 +429,75 @@ def test_colmajor_forms_match_rowmajor(device, m, K, beta):
     assert torch.equal(dCc.t(), dC)
 
 
+_tall: dict = {}
+
+
+def _tall_case():
+    """m = 64 * 65535 + 1 rows (one more 64-row tile than a grid's y dimension takes),
+    k = 64, n = 3: one nonzero in every 8th row, full rows at 0, m - 2 and m - 1; with
+    the row-major product of spmm_csrmm_ex_f32 (checked against numpy in float64, the
+    rows without a nonzero exactly 0), once."""
+    if not _tall:
+        m, k, n = 64 * 65535 + 1, 64, 3
+        rng = np.random.default_rng(4194241)
+        deg = np.zeros(m, np.int64)
+        deg[::8] = 1
+        full = [0, m - 2, m - 1]
+        deg[full] = k
+        rp = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+        ci = np.empty(rp[-1], np.int32)
+        single = np.flatnonzero(deg == 1)
+        ci[rp[single]] = (single // 8) % k
+        for r in full:
+            ci[rp[r]:rp[r + 1]] = np.arange(k)
+        v = rng.uniform(-1, 1, ci.size).astype(np.float32)
+        B = rng.uniform(-1, 1, (k, n)).astype(np.float32)
+        drp, dci, dv, dB = _dev(rp, ci, v, B)
+        dC = torch.full((m, n), float("nan"), device="cuda")
+        _ops().csrmm(drp, dci, dv, dB, n=n, k=k, ldb=n, C=dC, ldc=n)
+        row = dC.cpu().numpy()
+        B64, v64 = B.astype(np.float64), v.astype(np.float64)
+        ref, absd = np.zeros((m, n)), np.zeros((m, n))
+        ref[single] = v64[rp[single], None] * B64[ci[rp[single]]]
+        absd[single] = np.abs(ref[single])
+        for r in full:
+            ref[r] = v64[rp[r]:rp[r + 1]] @ B64
+            absd[r] = np.abs(v64[rp[r]:rp[r + 1]]) @ np.abs(B64)
+        assert_normwise(row, ref, absd, TOL_F32, "tall row-major product")
+        assert not row[deg == 0].any(), "a row without a nonzero is not 0"
+        C0 = rng.uniform(-1, 1, (m, n)).astype(np.float32)
+        _tall.update(m=m, k=k, n=n, d=(drp, dci, dv, dB), row=row, C0=C0, empty=deg == 0)
+    return _tall
+
+
+@pytest.mark.parametrize("beta", [0.0, 1.0])
+@pytest.mark.parametrize("pad", [0, 3])
+def test_colmajor_c_past_the_tile_grid_limit(device, pad, beta):
+    """A column-major C (spmm_scsrmm's layout) of 4,194,241 rows: its transpose back has
+    65536 tile rows, one more than grid.y takes, so launch_transpose numbers the tiles
+    along grid.x. ldc = m and m + 3. The result is the row-major product of the same
+    call transposed, bit for bit; at beta = 1 plus C0 in float32 (fma(1, c, x) is one
+    rounded add, as numpy's). Rows without a nonzero hold 0 (C0 at beta = 1), and the
+    ldc padding and the guards keep their sentinel."""
+    from helpers import framed
+    t = _tall_case()
+    m, k, n = t["m"], t["k"], t["n"]
+    drp, dci, dv, dB = t["d"]
+    C0 = t["C0"]
+    init = C0 if beta != 0.0 else np.full_like(C0, np.nan)
+    dC, chk = framed(np.ascontiguousarray(init.T), m + pad, 0)
+    _ops().csrmm(drp, dci, dv, dB, m=m, n=n, k=k, ldb=n, C=dC, ldc=m + pad,
+                 order_c=_ops().ORDER_COL, beta=beta)
+    got = chk(f"ldc = m + {pad}, beta = {beta}: C").T
+    want = t["row"] if beta == 0.0 else t["row"] + C0
+    assert want.dtype == np.float32
+    bad = got.view(np.uint32) != want.view(np.uint32)
+    assert not bad.any(), (f"{int(bad.sum())} elements differ from the transposed row-major "
+                           f"product, first in row {int(np.flatnonzero(bad.any(axis=1))[0])}")
+    rest = got[t["empty"]]
+    assert np.array_equal(rest, C0[t["empty"]] if beta != 0.0 else np.zeros_like(rest))
+
+
 @pytest.mark.parametrize("K,opts,alpha,beta", [
     (128, 0, 1.0, 0.0), (512, 0, 1.0, 0.0), (256, 0, 1.0, 0.0), (32, 2, 1.0, 0.0),
     (64, 0, 1.0, 0.0), (128, 0, 2.0, 0.5), (512, 0, -0.5, 2.0), (256, 0, 0.25, -1.0),

@@ -64,7 +64,13 @@ bs 64, to the generic kernel; bs 2 / 8 take the lane-group VALU kernel at two
 floats per lane when B is 8-byte aligned with an even ldb, else one. Neither
 entry documents an alignment requirement for bsrVal, and every kernel a
 misaligned bsrVal reaches (generic, lane-group VALU) loads it one element at a
-time, so those cases expect the product."""
+time, so those cases expect the product. The BSR tests also run ALIGNED_LAYOUTS_F32 /
+ALIGNED_LAYOUTS_F16 (helpers.py: 16-byte bases off the allocation's 256-byte one, ld a
+multiple of 16 bytes, so every fast path stays) and a column-major B (ldb = K + pad_B at
+off_B): with ROW blocks and n a multiple of the 16-byte vector it is staged row-major and
+tight (bsrmm_staged: transpose4_kernel / transpose16x4_kernel read it from any element
+base and ld), otherwise the direct kernels read it (register-fragment with a 16-byte B
+and ldb % 4 (8) == 0, else generic)."""
 from __future__ import annotations
 
 import ctypes
@@ -72,8 +78,9 @@ import ctypes
 import numpy as np
 import pytest
 
-from helpers import (TOL_F16_ACC, TOL_F32, assert_normwise, framed, oracle_bsrmm_f64,
-                     oracle_csrmm_d, oracle_csrmm_f64, oracle_csrmm_pieces_f32)
+from helpers import (ALIGNED_LAYOUTS_F16, ALIGNED_LAYOUTS_F32, TOL_F16_ACC, TOL_F32, assert_normwise,
+                     framed, long_row_column_sparse_bsr, oracle_bsrmm_f64, oracle_csrmm_d,
+                     oracle_csrmm_f64, oracle_csrmm_pieces_f32)
 
 pytestmark = pytest.mark.gpu
 
@@ -543,8 +550,11 @@ def _bsr_case(oracle, bs, n, direction, half):
 
 
 def _bsr_layouts(oracle, bs, n, direction, ab, half):
-    """Row-major C on every layout, column-major C on the layouts that pad C, and
-    bsrVal one element into its buffer (row-major and column-major C, tight B / C)."""
+    """Row-major C on every layout (LAYOUTS and the 16-byte ones off the 256-byte base),
+    column-major C on the layouts that pad C, column-major B (ldb = K + pad_B, base at
+    off_B: the staging transposes or the direct column-major-B kernels) with either C
+    on the layouts that pad or offset B, and bsrVal one element into its buffer
+    (row-major and column-major C, tight B / C)."""
     alpha, beta = ab
     ops = _ops()
     mb, kb, rp, ci, v, B, C0, ref, absd = _bsr_case(oracle, bs, n, direction, half)
@@ -553,14 +563,16 @@ def _bsr_layouts(oracle, bs, n, direction, ab, half):
     mm = ops.bsrmm_f16 if half else ops.bsrmm
     drp, dci, dv = _dev(rp, ci, v)
     fv, chkV = framed(v.reshape(1, -1), v.size, 1)
-    cases = [(lay, 0, 0) for lay in LAYOUTS] + [(lay, 1, 0) for lay in LAYOUTS if lay[3]] + \
-        [((0, 0, 0, 0), 0, 1), ((0, 0, 0, 0), 1, 1)]
-    for lay, oc, voff in cases:
+    lays = LAYOUTS + (ALIGNED_LAYOUTS_F16 if half else ALIGNED_LAYOUTS_F32)
+    cases = [(lay, 0, 0, 0) for lay in lays] + [(lay, 0, 1, 0) for lay in lays if lay[3]] + \
+        [((0, 0, 0, 0), 0, 0, 1), ((0, 0, 0, 0), 0, 1, 1)] + \
+        [(lay, 1, oc, 0) for lay in lays if lay[0] or lay[1] for oc in (0, 1)]
+    for lay, ob, oc, voff in cases:
         what = (f"bsr {'f16' if half else 'f32'} bs={bs} n={n} dir={direction} layout={lay} "
-                f"order_c={oc} bsrVal+{voff} alpha={alpha} beta={beta}")
-        dB, chkB, ldb, dC, _, ldc, extract = _frames(B, _c_init(C0, beta), lay, 0, oc)
-        mm(drp, dci, fv[:v.size] if voff else dv, dB, mb=mb, kb=kb, n=n, bs=bs, ldb=ldb, C=dC,
-           ldc=ldc, order_c=oc, alpha=alpha, beta=beta, direction=direction)
+                f"order_b={ob} order_c={oc} bsrVal+{voff} alpha={alpha} beta={beta}")
+        dB, chkB, ldb, dC, _, ldc, extract = _frames(B, _c_init(C0, beta), lay, ob, oc)
+        mm(drp, dci, fv[:v.size] if voff else dv, dB, mb=mb, kb=kb, n=n, bs=bs, ldb=ldb,
+           order_b=ob, C=dC, ldc=ldc, order_c=oc, alpha=alpha, beta=beta, direction=direction)
         assert_normwise(extract(what), want64, scale, tol, what)
         chkB.unchanged(what + ": B")
     chkV.unchanged("bsrVal")
@@ -583,3 +595,52 @@ def test_bsrmm_f16_layouts(oracle, device, n, direction, ab):
     """spmm_bsrmm_ex_f16 (bs = 16; B's layout in halves, C's in floats) against the
     exact product of the same fp16 values within TOL_F16_ACC, as test_bsrmm_f16."""
     _bsr_layouts(oracle, 16, n, direction, ab, half=True)
+
+
+# the drop-in column streams' tight-run bits: fp32 layouts in floats, fp16 B parts in halves
+_STREAM_LAYOUTS = {False: [(0, 4, 0, 8)] + ALIGNED_LAYOUTS_F32,
+                   True: [(0, 8, 0, 8), (8, 0, 0, 0), (8, 8, 4, 8), (0, 16, 4, 8)]}
+_DEMOTED_LAYOUTS = {False: [(0, 1, 0, 0), (1, 3, 3, 1), (0, 0, 1, 0)],
+                    True: [(0, 4, 0, 0), (1, 3, 3, 1), (4, 0, 0, 0)]}
+
+
+@pytest.mark.parametrize("ab", ABS, ids=AB_IDS)
+@pytest.mark.parametrize("half", [False, True], ids=["bs32-f32", "bs16-f16"])
+def test_bsrmm_column_sparse_long_rows_layouts(oracle, device, half, ab):
+    """The drop-in bs 32 fp32 and bs 16 fp16 products (ROW blocks, n = 136) on the matrix
+    of test_bsrmm_analysed / test_bsrmm_analysed_f16: column-sparse blocks (masked-out
+    columns, explicit zero and single-column blocks), an empty block row and one of
+    300 blocks (segments at bs 32). On the layouts that keep the column stream
+    ((0,4,0,8) in floats / (0,8,0,8) in halves and the 16-byte bases off the 256-byte
+    one) the result is the tight run's, bit for bit; on a demoted layout it is within
+    the bar."""
+    alpha, beta = ab
+    ops = _ops()
+    bs, mb, kb, n = (16, 21, 320, 136) if half else (32, 23, 320, 136)
+    key = ("long", half)
+    if key not in _bsr_cache:
+        rng = np.random.default_rng(320 + bs)
+        rp, ci, v = long_row_column_sparse_bsr(rng, mb, kb, bs)
+        vt = np.float16 if half else np.float32
+        v = v.astype(vt)
+        B = rng.uniform(-1, 1, (kb * bs, n)).astype(vt)
+        C0 = rng.uniform(-1, 1, (mb * bs, n)).astype(np.float32)
+        ref, absd = oracle_bsrmm_f64(oracle, 0, mb, n, bs, rp, ci, v, B, n, 0, half=half)
+        _bsr_cache[key] = rp, ci, v, B, C0, ref, absd
+    rp, ci, v, B, C0, ref, absd = _bsr_cache[key]
+    want64, scale = _expect(ref, absd, C0, alpha, beta)
+    tol = TOL_F16_ACC if half else TOL_F32
+    mm = ops.bsrmm_f16 if half else ops.bsrmm
+    drp, dci, dv = _dev(rp, ci, v)
+    tight = None
+    for lay in [(0, 0, 0, 0)] + _STREAM_LAYOUTS[half] + _DEMOTED_LAYOUTS[half]:
+        what = f"long rows {'f16' if half else 'f32'} bs={bs} layout={lay} alpha={alpha} beta={beta}"
+        dB, chkB, ldb, dC, _, ldc, extract = _frames(B, _c_init(C0, beta), lay)
+        mm(drp, dci, dv, dB, mb=mb, kb=kb, n=n, bs=bs, ldb=ldb, C=dC, ldc=ldc, alpha=alpha, beta=beta)
+        got = extract(what)
+        assert_normwise(got, want64, scale, tol, what)
+        chkB.unchanged(what + ": B")
+        if tight is None:
+            tight = got
+        elif lay in _STREAM_LAYOUTS[half]:
+            assert _same_bits(got, tight), what + ": bits differ from the tight run"

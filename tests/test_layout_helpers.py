@@ -1,7 +1,9 @@
 """framed() (tests/helpers.py) on the host: the layout it builds and the
 checker's guard check, which must fail for one changed word of every sentinel
 region and pass when only the data region changes (so the GPU layout tests'
-"padding untouched" assertions cannot pass vacuously)."""
+"padding untouched" assertions cannot pass vacuously). And the case lists of the
+grouped entries' layout tests against the header's documented contract, so that a
+later edit of a list cannot silently empty a class."""
 from __future__ import annotations
 
 import numpy as np
@@ -140,3 +142,81 @@ def test_integer_arrays_take_their_own_fill():
     chk.buffer[FRAME_GUARD] = 5
     with pytest.raises(AssertionError, match="offset gap changed"):
         chk("colind")
+
+
+# ------------------------------------------ the grouped entries' case lists
+# The documented contract of the two grouped products, restated from include/spmm_hip.h
+# (not from the launchers): the causes of SPMM_STATUS_NOT_SUPPORTED for a case
+# (n, order_b, order_c, (off_B, pad_B, off_C, pad_C)) on operands made by framed().
+_GROUPED = {  # itemsize of B, unit of n and ldb, (K, M) of the tests' matrix, the tests' n
+    "f32": (4, 4, (60 * 32, 37 * 32), (64, 132)),
+    "f16": (2, 8, (60 * 16, 37 * 16), (136, 264)),
+}
+
+
+def _address(off, itemsize):
+    """Address modulo 256 of a framed() view: the allocation is 256-byte aligned and the
+    front guard FRAME_GUARD elements long."""
+    return (FRAME_GUARD + off) * itemsize % 256
+
+
+def _causes(kind, n, ob, oc, lay):
+    size_b, unit, (K, M), _ = _GROUPED[kind]
+    off_b, pad_b, off_c, pad_c = lay
+    ldb = (n if ob == 0 else K) + pad_b
+    ldc = (n if oc == 0 else M) + pad_c
+    causes = set()
+    if n % unit:
+        causes.add("n")
+    if ob == 0 and ldb % unit:
+        causes.add("ldb")
+    if _address(off_b, size_b) % 16:
+        causes.add("B base")
+    if kind == "f32":  # "a row-major ldb or ldc % 4 != 0, or B or C is not 16-B aligned"
+        if oc == 0 and ldc % 4:
+            causes.add("ldc")
+        if _address(off_c, 4) % 16:
+            causes.add("C base")
+    return causes
+
+
+@pytest.mark.parametrize("kind", ["f32", "f16"])
+def test_grouped_case_lists_reach_what_they_claim(kind):
+    """The rejected list holds every documented cause alone at least once (and nothing
+    the header accepts), the accepted list no case that matches a cause."""
+    import helpers
+    accepted = getattr(helpers, f"GROUPED_{kind.upper()}_ACCEPTED")
+    rejected = getattr(helpers, f"GROUPED_{kind.upper()}_REJECTED")
+    ns = _GROUPED[kind][3]
+    alone = set()
+    for cn, ob, oc, lay in rejected:
+        for n in ([cn] if cn else ns):
+            causes = _causes(kind, n, ob, oc, lay)
+            assert len(causes) == 1, f"{(cn, ob, oc, lay)} at n={n}: causes {sorted(causes)}"
+            alone |= causes
+    want = {"n", "ldb", "B base"} | ({"ldc", "C base"} if kind == "f32" else set())
+    assert alone == want
+    for cn, ob, oc, lay in accepted:
+        for n in ([cn] if cn else ns):
+            assert not _causes(kind, n, ob, oc, lay), f"{(cn, ob, oc, lay)} at n={n} is rejected"
+    if kind == "f32":  # the residues the issue of each cause names
+        lays = [c[3] for c in rejected]
+        assert {l[1] % 4 for l in lays if l[1]} >= {1, 2} and {l[3] % 4 for l in lays if l[3]} >= {1, 2}
+        assert {l[0] for l in lays if l[0]} >= {1, 2} and {l[2] for l in lays if l[2]} >= {1, 2}
+        assert any(c[1] == 1 and c[3][0] for c in rejected) and any(c[2] == 1 and c[3][2] for c in rejected)
+
+
+def test_accepted_fp32_lists_leave_the_256_byte_base():
+    """Every fp32 list of layouts on which a fast path is asserted holds a base that is
+    16-byte but not 256-byte aligned, for B and for C."""
+    from helpers import ALIGNED_LAYOUTS_F32, GROUPED_F32_ACCEPTED
+    from test_gpu_layout import _STREAM_LAYOUTS
+    from test_gpu_layout_analysed import AN32_STREAM
+    lists = {"ALIGNED_LAYOUTS_F32": ALIGNED_LAYOUTS_F32,
+             "GROUPED_F32_ACCEPTED": [c[3] for c in GROUPED_F32_ACCEPTED],
+             "GROUPED_F32_ACCEPTED, row-major": [c[3] for c in GROUPED_F32_ACCEPTED if c[1:3] == (0, 0)],
+             "AN32_STREAM": AN32_STREAM, "_STREAM_LAYOUTS[fp32]": _STREAM_LAYOUTS[False]}
+    for name, lays in lists.items():
+        for i, operand in ((0, "B"), (2, "C")):
+            addr = [_address(lay[i], 4) for lay in lays]
+            assert any(a % 256 != 0 and a % 16 == 0 for a in addr), f"{name}: no such {operand} base"
