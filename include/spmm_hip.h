@@ -611,10 +611,12 @@ spmm_status_t spmm_hybrid_csrmm_f32(spmm_handle_t handle, int m, int n, int k, f
  * (ldc = nb*bs) with alpha = beta = 1, B column-major (transB = N, ldb >= k)
  * or row-major (transB = T, ldb >= n). Row-major B and C are
  * spmm_hybrid_csrmm_f32. Otherwise two stream-ordered launches: a
- * column-major B is transposed once into the handle's scratch (zero rows
- * past k, so ldb need only cover the k real rows), the BSR part writes C in
- * orderC with beta, then the CSR remainder accumulates. A column-major C
- * needs ldc >= ceil(m/bs)*bs when nnzb > 0 (>= m otherwise). */
+ * column-major B is transposed once into a staging buffer of the handle's
+ * that no kernel of the call writes (zero rows past k, so ldb need only cover
+ * the k real rows; a row-major B must hold ceil(k/bs)*bs rows when nnzb > 0,
+ * as for spmm_hybrid_csrmm_f32), the BSR part writes C in orderC with beta,
+ * then the CSR remainder accumulates. A column-major C needs
+ * ldc >= ceil(m/bs)*bs when nnzb > 0 (>= m otherwise). */
 spmm_status_t spmm_hybrid_csrmm_ex_f32(spmm_handle_t handle, int m, int n, int k, float alpha,
                                        const int* csrRowPtr, const int* csrColInd,
                                        const float* csrVal, int csrNnz, int blockDim,

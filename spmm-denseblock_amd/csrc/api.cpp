@@ -509,11 +509,15 @@ extern "C" spmm_status_t spmm_hybrid_csrmm_f32(
 // Row-major B and C keep spmm_hybrid_csrmm_f32 (fused when it pays). Any
 // column-major operand runs as two stream-ordered launches: a column-major B
 // is transposed once into a row-major (ceil(k/bs)*bs) x n copy in the handle's
-// scratch, zero rows past k (so the BSR part never reads past the caller's B:
-// the reference's ldb = n is short of nb*bs when bs does not divide n); the
-// BSR part runs the dense-block MFMA kernel on it, writing C in the caller's
-// order through its own epilogue (beta), then the CSR remainder accumulates
-// (beta = 1; a column-major C through the workspace transpose).
+// staging buffer (stage), zero rows past k (so the BSR part never reads past the
+// caller's B: the reference's ldb = n is short of nb*bs when bs does not divide
+// n); the BSR part runs on it (the dense-block MFMA kernel at bs 32, the kernel
+// of its block size elsewhere), writing C in the caller's order through its own
+// epilogue (beta), then the CSR remainder accumulates (beta = 1; a column-major C
+// through the workspace transpose). Both products read the copy and both write
+// handle buffers of their own (scratch: probe sums and dirty flags at bs 64 and
+// 2 / 4 / 8; order; ws: carries and the staged C), so the copy lives in none of
+// them, and stage is sized before anything is queued and by nothing else.
 extern "C" spmm_status_t spmm_hybrid_csrmm_ex_f32(
     spmm_handle_t handle, int m, int n, int k, float alpha, const int* csrRowPtr,
     const int* csrColInd, const float* csrVal, int csrNnz, int blockDim, const int* bsrRowPtr,
@@ -541,9 +545,9 @@ extern "C" spmm_status_t spmm_hybrid_csrmm_ex_f32(
   int ldbx = ldb;
   if (orderB == SPMM_ORDER_COL && k > 0) {
     const size_t rows_b = nnzb > 0 ? (size_t)kb * blockDim : (size_t)k;
-    spmm_status_t st = ensure_scratch(handle, rows_b * n * sizeof(float));
+    spmm_status_t st = ensure_stage(handle, rows_b * n * sizeof(float));
     if (st != SPMM_STATUS_SUCCESS) return st;
-    float* Bt = static_cast<float*>(handle->scratch);
+    float* Bt = static_cast<float*>(handle->stage);
     // B (k x n col-major) is an (n x k) row-major matrix with ld ldb
     st = launch_transpose(handle, n, k, B, ldb, Bt, n, 0.f);
     if (st != SPMM_STATUS_SUCCESS) return st;

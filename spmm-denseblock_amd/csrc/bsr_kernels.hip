@@ -4118,9 +4118,7 @@ spmm_status_t launch_bsrmm_f32(spmm_context* ctx, spmm_direction_t dir, int mb, 
     const dim3 grid(mb, (n + 127) / 128);
     const bool narrow = (size_t)ldb * 128 < (1u << 31);  // 32-row panels addressable in 31 bits
     int lv = dense_blocks ? kBsr32Dense : kBsr32Cs;
-    // (a tuning override never replaces the dense-block kernel: the hybrid's
-    // column-major form stages B in the handle scratch the column stream's
-    // segments would reuse)
+    // (a tuning override never replaces the dense-block kernel)
     if (!dense_blocks && (var == kBsr32CsNoNt || var == kBsr32CsWideLdb || var == kBsr32Cs))
       lv = var;
     if (!narrow && (lv == kBsr32Cs || lv == kBsr32CsNoNt)) lv = kBsr32CsWideLdb;

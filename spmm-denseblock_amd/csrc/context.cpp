@@ -35,6 +35,10 @@ spmm_status_t ensure_scratch(spmm_context* ctx, size_t bytes) {
   return grow_buffer(ctx, ctx->scratch, ctx->scratch_bytes, bytes);
 }
 
+spmm_status_t ensure_stage(spmm_context* ctx, size_t bytes) {
+  return grow_buffer(ctx, ctx->stage, ctx->stage_bytes, bytes);
+}
+
 spmm_status_t ensure_group_pending(spmm_context* ctx, size_t bytes) {
   return grow_buffer(ctx, ctx->grp_pend, ctx->grp_pend_bytes, bytes);
 }
@@ -169,9 +173,10 @@ spmm_status_t spmm_create(spmm_handle_t* handle) {
 spmm_status_t spmm_destroy(spmm_handle_t h) {
   if (!h) return SPMM_STATUS_NOT_INITIALIZED;
   if (h->grp_cols) (void)hipFreeAsync(h->grp_cols, h->stream);
-  if (h->ws || h->scratch || h->order || h->tickets || h->grp_pend || h->grp_cols)
+  if (h->ws || h->scratch || h->stage || h->order || h->tickets || h->grp_pend || h->grp_cols)
     (void)hipStreamSynchronize(h->stream);
   if (h->ws) (void)hipFree(h->ws);
+  if (h->stage) (void)hipFree(h->stage);
   if (h->grp_pend) (void)hipFree(h->grp_pend);
   if (h->tickets) (void)hipFree(h->tickets);
   if (h->scratch) (void)hipFree(h->scratch);

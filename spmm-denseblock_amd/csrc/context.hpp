@@ -38,10 +38,18 @@ struct spmm_context {
   // Device workspace (grown, never shrunk; freed in spmm_destroy).
   void* ws = nullptr;
   size_t ws_bytes = 0;
-  // Kernel scratch (item records, segment partial tiles), apart from ws: ws may
-  // hold a staged (transposed) B that the kernel reading it must not overwrite.
+  // Kernel scratch (segment partial tiles, probe sums, dirty flags, hot-column
+  // counts), apart from ws: ws may hold a staged (transposed) B that the kernel
+  // reading it must not overwrite. The launchers own it: no entry point keeps
+  // anything there across a launch.
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
+  // The hybrid's staged B (spmm_hybrid_csrmm_ex_f32 with a column-major B): read
+  // by both of the call's products, the BSR part (which writes scratch and order)
+  // and the CSR remainder (which carves up ws), so it lives in neither. Sized once
+  // per call, before anything is queued; no launcher touches it.
+  void* stage = nullptr;
+  size_t stage_bytes = 0;
   // Block-row order of the column-stream BSR kernels (mb ints, grown like ws).
   int* order = nullptr;
   size_t order_cap = 0;
@@ -101,6 +109,8 @@ namespace spmm {
 spmm_status_t ensure_workspace(spmm_context* ctx, size_t bytes);
 // The same for the kernel scratch buffer.
 spmm_status_t ensure_scratch(spmm_context* ctx, size_t bytes);
+// The same for the hybrid's staged B (stage).
+spmm_status_t ensure_stage(spmm_context* ctx, size_t bytes);
 // The same for the block-row order buffer (at least n ints).
 spmm_status_t ensure_order_buffer(spmm_context* ctx, size_t n);
 // The same for the pending group analysis (grp_pend).

@@ -408,3 +408,169 @@ def oracle_reorder(L, kind: str, rowptr, colind, perm=None):
 
 def load_reorder_golden():
     return np.load(os.path.join(GOLDEN, "ref_reorder.npz"), allow_pickle=False)
+
+
+# ----------------------------------------- hybrid entry with storage orders
+# (tests/test_gpu_hybrid_ex.py runs them, tests/test_gpu_handle_reuse.py reuses the
+# matrices, tests/test_hybrid_helpers.py checks on the host that they reach what the
+# tests claim)
+HYBRID_EX_M = 700
+# prep.divide density per block size at which the community matrix below keeps both a
+# BSR part and a CSR remainder; 5 is a block size only bsr_generic_kernel takes
+HYBRID_EX_DENSITY = {2: 0.5, 4: 0.3, 8: 0.2, 16: 0.2, 32: 0.1, 64: 0.1, 5: 0.2}
+HYBRID_EX_ORDERS = [(1, 1), (0, 1), (1, 0)]  # (order_b, order_c): transB = N, T, the mixed form
+HYBRID_EX_N = [64, 136, 7]
+# (off_B, pad_B, off_C, pad_C) in floats: tight, 16-byte friendly, off 16 bytes
+HYBRID_EX_LAYOUTS = [(0, 0, 0, 0), (4, 4, 4, 4), (1, 1, 1, 3)]
+_hybrid_ex_cache: dict = {}
+
+
+def hybrid_ex_matrix():
+    """The 700 x 700 community matrix of test_hybrid_divide_spmm with uniform(-1, 1)
+    values -> (rowptr, colind, val)."""
+    if "A" not in _hybrid_ex_cache:
+        from spmm_hip import prep
+        rp, ci = prep.community_csr(HYBRID_EX_M, 40.0, 48, 160, 0.9, 3)
+        v = np.random.default_rng(4).uniform(-1, 1, ci.size).astype(np.float32)
+        _hybrid_ex_cache["A"] = rp, ci, v
+    return _hybrid_ex_cache["A"]
+
+
+def hybrid_ex_parts(bs):
+    """prep.divide of hybrid_ex_matrix() at HYBRID_EX_DENSITY[bs] ->
+    (csr_rp, csr_ci, csr_v, bsr_rp, bsr_ci, bsr_v)."""
+    if bs not in _hybrid_ex_cache:
+        from spmm_hip import prep
+        rp, ci, v = hybrid_ex_matrix()
+        _hybrid_ex_cache[bs] = prep.divide(HYBRID_EX_M, rp, ci, v, bs, HYBRID_EX_DENSITY[bs])
+    return _hybrid_ex_cache[bs]
+
+
+def framed_operands(Bd, Cd, lay, ob=0, oc=0, device="cuda"):
+    """Bd (rows_b x n) and Cd (rows_c x n) framed in the given storage orders on
+    lay = (off_B, pad_B, off_C, pad_C): a column-major operand's framed rows are its
+    columns and its ld is its row count plus the pad. Returns (B view, B checker, ldb,
+    C view, ldc, extract) with extract(what) the guard-checked rows_c x n result."""
+    off_b, pad_b, off_c, pad_c = lay
+    B2 = Bd if ob == 0 else np.ascontiguousarray(Bd.T)
+    C2 = Cd if oc == 0 else np.ascontiguousarray(Cd.T)
+    ldb, ldc = B2.shape[1] + pad_b, C2.shape[1] + pad_c
+    dB, chkB = framed(B2, ldb, off_b, device=device)
+    dC, chkC = framed(C2, ldc, off_c, device=device)
+
+    def extract(what):
+        got = chkC(what + ": C")
+        return got if oc == 0 else np.ascontiguousarray(got.T)
+    return dB, chkB, ldb, dC, ldc, extract
+
+
+def hybrid_ex_staged_b_bytes(k, bs, n):
+    """Bytes of the hybrid's staged copy of a column-major B: ceil(k / bs) * bs rows of
+    n floats."""
+    return -(-k // bs) * bs * n * 4
+
+
+def small_grouped_scratch_bytes(m, bs, n):
+    """Scratch of the bs 2 / 4 / 8 grouped branch (launch_bsrmm_f32): the probe's sums
+    in bytes 0..15, one dirty flag per (group of 32 / bs block rows, 128-column tile)
+    from byte 256."""
+    mb = -(-m // bs)
+    return -(-mb // (32 // bs)) * -(-n // 128) * 4 + 256
+
+
+PANEL_MIN_BLOCKS = 1 << 15  # kPanelMinBlocks (bsr_kernels.hip): 32 x 32 sub-blocks from which the probe runs
+PROBE64_MB, PROBE64_N = 128, 8
+PROBE64_CHECKED_BLOCK_ROWS = (0, 41, 86, 127)
+
+
+def panel_probe_bsr64(seed=64):
+    """The smallest bs 64 matrix whose product launches panel_probe_kernel
+    (4 * nnzb >= kPanelMinBlocks): 128 x 128 block rows / columns, every block row
+    holding block column 0 and 63 others, all 8192 blocks fully dense (134 MB), and a
+    CSR remainder of three entries per row, one of them in columns 0..3 in every
+    fourth row. -> (brp, bci, bval, crp, cci, cv)."""
+    rng = np.random.default_rng(seed)
+    mb = PROBE64_MB
+    cols = [np.concatenate([[0], 1 + np.sort(rng.choice(mb - 1, 63, replace=False))])
+            for _ in range(mb)]
+    brp = (64 * np.arange(mb + 1)).astype(np.int32)
+    bci = np.concatenate(cols).astype(np.int32)
+    bval = rng.random(bci.size * 4096, dtype=np.float32)
+    bval *= 2.0
+    bval -= 1.0
+    m = mb * 64
+    cci = rng.integers(0, m, (m, 3))
+    cci[::4, 0] = rng.integers(0, 4, cci[::4, 0].size)
+    cci = np.sort(cci, axis=1)
+    crp = (3 * np.arange(m + 1)).astype(np.int32)
+    cv = rng.uniform(-1, 1, cci.size).astype(np.float32)
+    return brp, bci, bval, crp, cci.reshape(-1).astype(np.int32), cv
+
+
+def probe64_block_row_reference(br, mats, Bd):
+    """float64 (ref, absdot) of block row br of panel_probe_bsr64's matrix times
+    Bd (8192 x n): its dense 64 x 8192 slab, BSR blocks plus CSR remainder (an entry
+    both parts hold is added, as the two products add it), and the slab of absolute
+    values."""
+    brp, bci, bval, crp, cci, cv = mats
+    k = PROBE64_MB * 64
+    slab, aslab = np.zeros((64, k)), np.zeros((64, k))
+    for j in range(brp[br], brp[br + 1]):
+        blk = bval[j * 4096:(j + 1) * 4096].reshape(64, 64).astype(np.float64)
+        slab[:, bci[j] * 64:bci[j] * 64 + 64] = blk
+        aslab[:, bci[j] * 64:bci[j] * 64 + 64] = np.abs(blk)
+    for r in range(64):
+        row = br * 64 + r
+        for j in range(crp[row], crp[row + 1]):
+            slab[r, cci[j]] += float(cv[j])
+            aslab[r, cci[j]] += abs(float(cv[j]))
+    B64 = Bd.astype(np.float64)
+    return slab @ B64, aslab @ np.abs(B64)
+
+
+def rand_csr_rows(rng, m, k, deg_hi, empty_frac=0.2):
+    """A random m x k CSR: 0..deg_hi sorted distinct columns per row, some rows empty,
+    uniform(-1, 1) values."""
+    deg = rng.integers(0, deg_hi + 1, m)
+    deg[rng.random(m) < empty_frac] = 0
+    rp = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+    ci = (np.concatenate([np.sort(rng.choice(k, d, replace=False)) for d in deg]).astype(np.int32)
+          if rp[-1] else np.zeros(0, np.int32))
+    return rp, ci, rng.uniform(-1, 1, ci.size).astype(np.float32)
+
+
+# ------------------------------------------------- handle reuse: step inputs
+REUSE_HUB_M, REUSE_HUB_K, REUSE_HUB_NNZ = 3000, 50000, 40000
+CSR_PIECE_MIN = 128  # a CSR row longer than this is cut into pieces (DESIGN.md §3c)
+REUSE_SEG_SHAPE = (23, 320, 32, 136)  # mb, kb, bs, n of step d
+
+
+def reuse_hub_csr(seed=2024):
+    """Step a's matrix: 3000 x 50000, rows of 0..6 nonzeros (30 % empty) and one hub
+    row of 40,000."""
+    rng = np.random.default_rng(seed)
+    deg = rng.integers(0, 7, REUSE_HUB_M)
+    deg[rng.random(REUSE_HUB_M) < 0.3] = 0
+    rows = [np.unique(rng.integers(0, REUSE_HUB_K, d)) for d in deg]
+    rows[1234] = np.sort(rng.choice(REUSE_HUB_K, REUSE_HUB_NNZ, replace=False))
+    rp = np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int32)
+    ci = np.concatenate(rows).astype(np.int32)
+    return rp, ci, rng.uniform(-1, 1, ci.size).astype(np.float32)
+
+
+def cs2_segments_splits(rowptr, ntiles, num_cus=256):
+    """cs2_segments' rule (bsr_kernels.hip) restated: on a shallow grid (at most
+    kLptRounds = 8 rounds of the 12 * num_cus wave slots), when the longest block row
+    holds more than twice the mean load per wave slot (2 nnzb / slots blocks), the
+    rows longer than L = max(64, nnzb / (2 * slots)) blocks are split. Returns the
+    number of rows it splits."""
+    rowptr = np.asarray(rowptr, np.int64)
+    mb, nnzb = rowptr.size - 1, int(rowptr[-1])
+    slots = 12 * num_cus
+    if nnzb <= 0 or mb * ntiles > 8 * slots:
+        return 0
+    L = max(64, -(-nnzb // (2 * slots)))
+    lens = np.diff(rowptr)
+    if lens.max() <= 2 * -(-nnzb // slots):  # rounded up: the stricter reading
+        return 0
+    return int((lens > L).sum())
