@@ -200,6 +200,24 @@ spmm_status_t spmm_csrmm_ex_f32(spmm_handle_t handle, int m, int n, int k, int n
                                 const float* B, int ldb, spmm_order_t orderB, float beta,
                                 float* C, int ldc, spmm_order_t orderC);
 
+/* fp16 A values and B, fp32 accumulate, C, alpha and beta (fp16 as uint16_t bit
+ * patterns, as in spmm_bsrmm_ex_f16): the checks, quick returns and ld rules of
+ * spmm_csrmm_ex_f32 / spmm_gespmm_csrmm_f32, ldb counted in halves. binary16 widens
+ * to binary32 exactly (subnormals included), so C is, bit for bit and signed zeros
+ * included, what spmm_csrmm_ex_f32 gives on the widened inputs under
+ * SPMM_CSR_SEQUENTIAL_ROWS: the piece association of the merge-path kernel at every n,
+ * whatever the grid, the row shard, the entry point, the storage orders or B's
+ * alignment (a B at an odd half offset or with an odd ldb is gathered one half per
+ * lane). A column-major B is staged through the handle workspace in halves. */
+spmm_status_t spmm_csrmm_ex_f16(spmm_handle_t handle, int m, int n, int k, int nnz,
+                                float alpha, const int* csrRowPtr, const int* csrColInd,
+                                const uint16_t* csrVal, spmm_index_base_t base,
+                                const uint16_t* B, int ldb, spmm_order_t orderB, float beta,
+                                float* C, int ldc, spmm_order_t orderC);
+spmm_status_t spmm_gespmm_csrmm_f16(int A_nrows, int B_ncols, const int* A_rowPtr,
+                                    const int* A_colInd, const uint16_t* A_val,
+                                    const uint16_t* B, float* C, void* stream);
+
 /* Hot-column analysis for the CSR gathers (an extension, once per matrix like
  * cuSPARSE's SpMM preprocess; the reference's gespmm_csrmm.h / csrmm.cu have
  * none). Counts every column's nonzeros on the device and writes

@@ -16,14 +16,17 @@ struct WsLayout {
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// T: float, or uint16_t for binary16 A values and B (fp32 C either way; no hot form)
+template <typename T>
 spmm_status_t csrmm_impl(spmm_context* ctx, int m, int n, int k, int nnz_hint, float alpha,
-                         const int* rowptr, const int* colind, const float* val, int base,
-                         const float* B, int ldb, spmm_order_t orderB, float beta, float* C,
+                         const int* rowptr, const int* colind, const T* val, int base,
+                         const T* B, int ldb, spmm_order_t orderB, float beta, float* C,
                          int ldc, spmm_order_t orderC, bool hot = false) {
+  constexpr bool f16 = sizeof(T) == 2;
   WsLayout L;
   L.carry_bytes = csrmm_carry_bytes(ctx, m, n);
   L.b_off = align256(L.carry_bytes);
-  const size_t b_bytes = orderB == SPMM_ORDER_COL ? (size_t)k * n * sizeof(float) : 0;
+  const size_t b_bytes = orderB == SPMM_ORDER_COL ? (size_t)k * n * sizeof(T) : 0;
   L.c_off = align256(L.b_off + b_bytes);
   const size_t c_bytes = orderC == SPMM_ORDER_COL ? (size_t)m * n * sizeof(float) : 0;
   L.total = L.c_off + c_bytes;
@@ -31,7 +34,7 @@ spmm_status_t csrmm_impl(spmm_context* ctx, int m, int n, int k, int nnz_hint, f
   if (st != SPMM_STATUS_SUCCESS) return st;
   char* ws = static_cast<char*>(ctx->ws);
 
-  const float* Bx = B;
+  const T* Bx = B;
   int ldbx = ldb;
   // hot-tagged indices: one buffer resource for all of B when every row offset
   // fits 32 bits (the kernel then passes the row in soffset)
@@ -40,19 +43,27 @@ spmm_status_t csrmm_impl(spmm_context* ctx, int m, int n, int k, int nnz_hint, f
   };
   if (orderB == SPMM_ORDER_COL) {
     // B (k x n col-major) is an (n x k) row-major matrix with ld ldb.
-    float* Bt = reinterpret_cast<float*>(ws + L.b_off);
-    st = launch_transpose(ctx, n, k, B, ldb, Bt, n, 0.f);
+    T* Bt = reinterpret_cast<T*>(ws + L.b_off);
+    if constexpr (f16)
+      st = launch_transpose16(ctx, n, k, B, ldb, Bt, n);
+    else
+      st = launch_transpose(ctx, n, k, B, ldb, Bt, n, 0.f);
     if (st != SPMM_STATUS_SUCCESS) return st;
     Bx = Bt;
     ldbx = n;
   }
-  if (orderC == SPMM_ORDER_ROW) {
-    return launch_csrmm_rowmajor(ctx, m, n, rowptr, colind, val, base, Bx, ldbx, alpha, beta, C,
-                                 ldc, ws, nnz_hint, hot_mode(ldbx));
-  }
+  // the row-major product into Cx (ldcx) with beta bx
+  auto product = [&](float bx, float* Cx, int ldcx) {
+    if constexpr (f16)
+      return launch_csrmm_rowmajor_f16(ctx, m, n, rowptr, colind, val, base, Bx, ldbx, alpha, bx,
+                                       Cx, ldcx, ws, nnz_hint);
+    else
+      return launch_csrmm_rowmajor(ctx, m, n, rowptr, colind, val, base, Bx, ldbx, alpha, bx, Cx,
+                                   ldcx, ws, nnz_hint, hot_mode(ldbx));
+  };
+  if (orderC == SPMM_ORDER_ROW) return product(beta, C, ldc);
   float* Ct = reinterpret_cast<float*>(ws + L.c_off);
-  st = launch_csrmm_rowmajor(ctx, m, n, rowptr, colind, val, base, Bx, ldbx, alpha, 0.f, Ct, n,
-                             ws, nnz_hint, hot_mode(ldbx));
+  st = product(0.f, Ct, n);
   if (st != SPMM_STATUS_SUCCESS) return st;
   // C (m x n col-major, ldc) is an (n x m) row-major matrix with ld ldc.
   return launch_transpose(ctx, m, n, Ct, n, C, ldc, beta);
@@ -120,6 +131,41 @@ spmm_status_t spmm_gespmm_csrmm_f32(int A_nrows, int B_ncols, const int* A_rowPt
 spmm_status_t spmm_csrmm_ex_f32(spmm_handle_t handle, int m, int n, int k, int nnz, float alpha,
                                 const int* csrRowPtr, const int* csrColInd, const float* csrVal,
                                 spmm_index_base_t base, const float* B, int ldb,
+                                spmm_order_t orderB, float beta, float* C, int ldc,
+                                spmm_order_t orderC) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if ((orderB != SPMM_ORDER_ROW && orderB != SPMM_ORDER_COL) ||
+      (orderC != SPMM_ORDER_ROW && orderC != SPMM_ORDER_COL))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && (!csrColInd || !csrVal)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (orderB == SPMM_ORDER_ROW ? ldb < n : ldb < (k > 0 ? k : 1)) return SPMM_STATUS_INVALID_VALUE;
+  if (orderC == SPMM_ORDER_ROW ? ldc < n : ldc < m) return SPMM_STATUS_INVALID_VALUE;
+  return csrmm_impl(handle, m, n, k, nnz, alpha, csrRowPtr, csrColInd, csrVal, (int)base, B, ldb,
+                    orderB, beta, C, ldc, orderC);
+}
+
+// The fp16-input forms of the two entries above: the same checks in the same order.
+spmm_status_t spmm_gespmm_csrmm_f16(int A_nrows, int B_ncols, const int* A_rowPtr,
+                                    const int* A_colInd, const uint16_t* A_val, const uint16_t* B,
+                                    float* C, void* stream) {
+  if (A_nrows < 0 || B_ncols < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (A_nrows == 0 || B_ncols == 0) return SPMM_STATUS_SUCCESS;
+  if (!A_rowPtr || !A_colInd || !A_val || !B || !C) return SPMM_STATUS_INVALID_VALUE;
+  spmm_context* ctx = default_context();
+  if (!ctx) return SPMM_STATUS_NOT_INITIALIZED;
+  ctx->stream = reinterpret_cast<hipStream_t>(stream);
+  return csrmm_impl(ctx, A_nrows, B_ncols, A_nrows, -1, 1.f, A_rowPtr, A_colInd, A_val, 0, B,
+                    B_ncols, SPMM_ORDER_ROW, 0.f, C, B_ncols, SPMM_ORDER_ROW);
+}
+
+spmm_status_t spmm_csrmm_ex_f16(spmm_handle_t handle, int m, int n, int k, int nnz, float alpha,
+                                const int* csrRowPtr, const int* csrColInd, const uint16_t* csrVal,
+                                spmm_index_base_t base, const uint16_t* B, int ldb,
                                 spmm_order_t orderB, float beta, float* C, int ldc,
                                 spmm_order_t orderC) {
   if (!handle) return SPMM_STATUS_NOT_INITIALIZED;

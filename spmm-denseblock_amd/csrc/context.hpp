@@ -142,6 +142,12 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
                                     const float* B, int ldb, float alpha, float beta, float* C,
                                     int ldc, void* carry_ws, int nnz_hint,
                                     int hot = 0);  // 1: hot-tagged colind; 2: and B below 4 GB
+// fp16 val and B (bit patterns), fp32 C: the merge-path kernel at every n, the same
+// carry_ws and tickets
+spmm_status_t launch_csrmm_rowmajor_f16(spmm_context* ctx, int m, int n, const int* rowptr,
+                                        const int* colind, const uint16_t* val, int base,
+                                        const uint16_t* B, int ldb, float alpha, float beta,
+                                        float* C, int ldc, void* carry_ws, int nnz_hint);
 // spmm_csr_hot_analysis: colind_out = colind with bit 31 set on hot columns
 spmm_status_t launch_csr_hot_analysis(spmm_context* ctx, int k, long long nnz, const int* colind,
                                       int base, long long hot_rows, int* colind_out);

@@ -63,6 +63,20 @@ template <int VEC>
 __device__ __forceinline__ typename Vec<VEC>::T vload(const float* p) {
   return *reinterpret_cast<const typename Vec<VEC>::T*>(p);
 }
+// The binary16 operands of the fp16-input form (spmm_csrmm_ex_f16): VEC halves in one
+// 2- / 4- / 8-byte load, widened (exactly) to the VEC floats the FMA chain takes.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <int VEC>
+__device__ __forceinline__ typename Vec<VEC>::T vload(const _Float16* p) {
+  if constexpr (VEC == 1) {
+    return (float)*p;
+  } else if constexpr (VEC == 2) {
+    return __builtin_convertvector(*reinterpret_cast<const f16x2*>(p), f32x2);
+  } else {
+    return __builtin_convertvector(*reinterpret_cast<const f16x4*>(p), f32x4);
+  }
+}
 template <int VEC>
 __device__ __forceinline__ void vstore(float* p, typename Vec<VEC>::T v) {
   *reinterpret_cast<typename Vec<VEC>::T*>(p) = v;
@@ -285,12 +299,24 @@ struct PieceState {
   __device__ __forceinline__ int npieces(int rs) const { return (re - rs + T - 1) / T; }
 };
 
+// The merge-path kernel for A values and B of type T: float, or _Float16 (fp16 input,
+// spmm_csrmm_ex_f16) widened to float where it lands (the chunk's values once per lane,
+// a gathered B piece per load: gathers of 2 / 4 / 8 bytes per lane over the same 64 /
+// 128 / 256-column tiles), so the walk, the pieces, the split rows and the epilogue are
+// one text, the slots and tickets one size, and an fp16-input product has the bits of
+// the fp32 product of the widened inputs. T is the enclosing struct's parameter rather
+// than the kernel's own so that the kernel's <VEC, NT, HOT> stays what the assembly
+// audits read in its symbol (tests/test_isa_hot.py); the struct holds nothing else, and
+// the kernel keeps a free function's indentation.
+template <typename T>
+struct CsrMp {
 template <int VEC, bool NT, int HOT = 0>
-__global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
+static __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
     int m, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
-    const float* __restrict__ val, int base, const float* __restrict__ B, int ldb, float alpha,
+    const T* __restrict__ val, int base, const T* __restrict__ B, int ldb, float alpha,
     float beta, float* __restrict__ C, int ldc, SplitWs sws, int* __restrict__ tickets,
     int nwaves) {
+  static_assert(HOT == 0 || sizeof(T) == 4, "the hot-column gathers address B in floats");
   typedef typename Vec<VEC>::T vec;
   const int lane = threadIdx.x & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerWG + (threadIdx.x >> 6));
@@ -352,11 +378,11 @@ __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
   size_t head_key = 0;
   int head_stored = 0, head_np = 0;
 
-  const float* Bb = B - (size_t)base * ldb;  // row 0 of B for 1-based colind
+  const T* Bb = B - (size_t)base * ldb;  // row 0 of B for 1-based colind
   float* Ct = C + col0;
   // HOT = 2 (every B offset below 4 GB): one resource for all of B, the row in soffset
   const __amdgpu_buffer_rsrc_t brs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Bb), 0, 0xffffffff, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Bb), 0, 0xffffffff, 0x00020000);
   const unsigned ldb4 = 4u * (unsigned)ldb;
 
   auto epi_store = [&](int row, const float (&x)[VEC]) {
@@ -463,19 +489,21 @@ __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
     float valv[kR];
     auto load_chunk = [&](int c) {
       const int cb = gs + c * (kChunk * kU) + kR * lane;
+      T raw[kR];  // the values as stored: widened once per lane below (fp16 input)
 #pragma unroll
       for (int r = 0; r < kR; ++r) {
         const int idx = min(cb + r, A1 - 1);
         if constexpr (NT) {
           colv[r] = __builtin_nontemporal_load(colind + idx);
-          valv[r] = __builtin_nontemporal_load(val + idx);
+          raw[r] = __builtin_nontemporal_load(val + idx);
         } else {
           colv[r] = colind[idx];
-          valv[r] = val[idx];
+          raw[r] = val[idx];
         }
       }
 #pragma unroll
       for (int r = 0; r < kR; ++r) {
+        valv[r] = (float)raw[r];
         settle(colv[r]);
         settle(valv[r]);
       }
@@ -492,7 +520,7 @@ __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
         vdst[u] = rdlanef(valv[u % kR], l);
         // Wave-uniform row base (SGPRs) + per-lane column offset.
         const int cr = rdlane(colv[u % kR], l);
-        const float* rowp = Bb + (size_t)(HOT ? (cr & 0x7fffffff) : cr) * ldb;
+        const T* rowp = Bb + (size_t)(HOT ? (cr & 0x7fffffff) : cr) * ldb;
         vec x;
         if constexpr (HOT == 2) {
           // the same with the row offset in soffset (no per-row resource: 6 fewer
@@ -511,7 +539,7 @@ __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
           // Buffer loads: the cache policy is an immediate of the intrinsic, so the
           // two arms stay two instructions (plain loads were merged, nt dropped).
           const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-              const_cast<float*>(rowp), 0, 0x7fffffff, 0x00020000);
+              const_cast<T*>(rowp), 0, 0x7fffffff, 0x00020000);
           if (cr < 0)
             x = bload<VEC, 0>(rs, 4 * col_ld);
           else
@@ -577,6 +605,8 @@ __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
     if (split_row_arrive(tickets + ps.key, ps.stored, np, lane)) finish(i1, ps.key, np);
   }
 }
+
+};  // struct CsrMp
 
 // Small-K form (K <= 64, K % 4 == 0): the wave is cut into G = 64 / LPG lane
 // groups of LPG lanes (LPG = 2 / 4 / 8 / 16 for K <= 8 / 16 / 32 / 64; lane l: group
@@ -942,13 +972,16 @@ __global__ __launch_bounds__(256) void transpose16x4_kernel(int rows, int cols,
   }
 }
 
-int pick_vec(int n, const float* B, int ldb, const float* C, int ldc) {
+// eb: bytes per element of B (4, or 2 for the fp16-input form, whose gathers need B's
+// alignment in halves: 8 bytes at VEC 4, 4 at VEC 2)
+int pick_vec(int n, const void* B, int ldb, const float* C, int ldc, int eb = 4) {
   auto aligned = [](const void* p, int bytes) {
     return (reinterpret_cast<uintptr_t>(p) % bytes) == 0;
   };
-  if (n > 128 && n % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned(B, 16) && aligned(C, 16))
+  if (n > 128 && n % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned(B, 4 * eb) &&
+      aligned(C, 16))
     return 4;
-  if (n > 64 && n % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 && aligned(B, 8) && aligned(C, 8))
+  if (n > 64 && n % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 && aligned(B, 2 * eb) && aligned(C, 8))
     return 2;
   return 1;
 }
@@ -1184,11 +1217,13 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
     return from_hip(hipGetLastError());
   }
 #define SPMM_LAUNCH_MP(V, N)                                                                   \
-  hipLaunchKernelGGL((csr_mergepath_kernel<V, N>), grid, block, 0, ctx->stream, m, n, rowptr, \
-                     colind, val, base, B, ldb, alpha, beta, C, ldc, sws, tickets, nw)
+  hipLaunchKernelGGL((CsrMp<float>::csr_mergepath_kernel<V, N>), grid, block, 0, ctx->stream,  \
+                     m, n, rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws,        \
+                     tickets, nw)
 #define SPMM_LAUNCH_HOT(V, H)                                                                  \
-  hipLaunchKernelGGL((csr_mergepath_kernel<V, true, H>), grid, block, 0, ctx->stream, m, n,    \
-                     rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws, tickets, nw)
+  hipLaunchKernelGGL((CsrMp<float>::csr_mergepath_kernel<V, true, H>), grid, block, 0,         \
+                     ctx->stream, m, n, rowptr, colind, val, base, B, ldb, alpha, beta, C,     \
+                     ldc, sws, tickets, nw)
   if (hot == 2) {
     if (vec == 4) SPMM_LAUNCH_HOT(4, 2); else if (vec == 2) SPMM_LAUNCH_HOT(2, 2); else SPMM_LAUNCH_HOT(1, 2);
   } else if (hot) {
@@ -1202,6 +1237,45 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
   }
 #undef SPMM_LAUNCH_MP
 #undef SPMM_LAUNCH_HOT
+  timing_end(ctx, slot);
+  return from_hip(hipGetLastError());
+}
+
+// The fp16-input form: always the merge-path kernel (at n <= 64 too, one 64-column tile
+// at VEC 1, so every n has the piece oracle's bits), the fp32 launch's grid, slots and
+// tickets.
+spmm_status_t launch_csrmm_rowmajor_f16(spmm_context* ctx, int m, int n, const int* rowptr,
+                                        const int* colind, const uint16_t* val, int base,
+                                        const uint16_t* B, int ldb, float alpha, float beta,
+                                        float* C, int ldc, void* carry_ws, int nnz_hint) {
+  if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  const int vec = pick_vec(n, B, ldb, C, ldc, 2);
+  const int tile = kWave * vec;
+  const int ntiles = (n + tile - 1) / tile;
+  const int nw = csr_nwaves(ctx, m, nnz_hint, false);
+  dim3 grid((nw + kWavesPerWG - 1) / kWavesPerWG, ntiles);
+  dim3 block(kWG);
+  SplitWs sws;
+  sws.slots = static_cast<float*>(carry_ws);
+  sws.stride = tile;
+  if (spmm_status_t st = ensure_tickets(ctx, (size_t)nw * ntiles)) return st;
+  int* tickets = ctx->tickets;
+  const _Float16* val16 = reinterpret_cast<const _Float16*>(val);
+  const _Float16* B16 = reinterpret_cast<const _Float16*>(B);
+  const int slot = timing_begin(ctx);
+  const bool nt = (ctx->csr_flags & SPMM_CSR_NT_STREAMS) != 0;
+#define SPMM_LAUNCH_MP16(V, N)                                                                 \
+  hipLaunchKernelGGL((CsrMp<_Float16>::csr_mergepath_kernel<V, N>), grid, block, 0,            \
+                     ctx->stream, m, n, rowptr, colind, val16, base, B16, ldb, alpha, beta, C, \
+                     ldc, sws, tickets, nw)
+  if (vec == 4) {
+    if (nt) SPMM_LAUNCH_MP16(4, true); else SPMM_LAUNCH_MP16(4, false);
+  } else if (vec == 2) {
+    if (nt) SPMM_LAUNCH_MP16(2, true); else SPMM_LAUNCH_MP16(2, false);
+  } else {
+    if (nt) SPMM_LAUNCH_MP16(1, true); else SPMM_LAUNCH_MP16(1, false);
+  }
+#undef SPMM_LAUNCH_MP16
   timing_end(ctx, slot);
   return from_hip(hipGetLastError());
 }

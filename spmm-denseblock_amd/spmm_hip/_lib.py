@@ -83,6 +83,9 @@ _PROTOS = {
                              _P, _P, _P, _P, c_int, POINTER(c_float), _P, c_int]),
     "spmm_csrmm_ex_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int,
                                   _P, c_int, c_int, c_float, _P, c_int, c_int]),
+    "spmm_csrmm_ex_f16": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int,
+                                  _P, c_int, c_int, c_float, _P, c_int, c_int]),
+    "spmm_gespmm_csrmm_f16": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "spmm_csr_hot_analysis": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_longlong, _P]),
     "spmm_csrmm_hot_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int,
                                    _P, c_int, c_int, c_float, _P, c_int, c_int]),

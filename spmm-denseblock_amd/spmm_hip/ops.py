@@ -9,6 +9,8 @@ through the C ABI. The functions mirror the reference's operator interfaces:
   csrmm(...)          cusparseScsrmm / csrmm2 with explicit storage orders
   bsrmm(...)          cusparseSbsrmm / rocsparse_bsrmm_template<float>
   bsrmm_f16(...)      fp16 A/B, fp32 accumulate (config 5)
+  csrmm_f16(...) / gespmm_csrmm_f16(...)
+                      csrmm / gespmm_csrmm with fp16 A/B, fp32 accumulate and C
 """
 from __future__ import annotations
 
@@ -156,6 +158,44 @@ def csrmm(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B: torc
     check(getattr(lib(), fn)(h.raw, m, n, k, colind.numel(), alpha, _ptr(rowptr), _ptr(colind),
                              _ptr(val), base, _ptr(B), ldb, order_b, beta, _ptr(C), ldc,
                              order_c), fn)
+    return C
+
+
+def csrmm_f16(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B: torch.Tensor, *,
+              m: int | None = None, n: int, k: int, ldb: int, order_b: int = ORDER_ROW,
+              C: torch.Tensor, ldc: int, order_c: int = ORDER_ROW, alpha: float = 1.0,
+              beta: float = 0.0, base: int = 0, handle: Handle | None = None) -> torch.Tensor:
+    """csrmm with fp16 A values and B, fp32 accumulate / C (spmm_csrmm_ex_f16): the
+    bits of csrmm on the widened inputs (the piece association at every n)."""
+    for t, d, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                     (val, torch.float16, "val"), (B, torch.float16, "B"),
+                     (C, torch.float32, "C")):
+        _need(t, d, nm)
+    h = handle or default_handle()
+    m = rowptr.numel() - 1 if m is None else m
+    check(lib().spmm_csrmm_ex_f16(h.raw, m, n, k, colind.numel(), alpha, _ptr(rowptr),
+                                  _ptr(colind), _ptr(val), base, _ptr(B), ldb, order_b, beta,
+                                  _ptr(C), ldc, order_c), "spmm_csrmm_ex_f16")
+    return C
+
+
+def gespmm_csrmm_f16(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor,
+                     B: torch.Tensor, C: torch.Tensor | None = None) -> torch.Tensor:
+    """gespmm_csrmm with fp16 val[nnz] and B[k, K]; returns the fp32 C[m, K]
+    (spmm_gespmm_csrmm_f16)."""
+    for t, d, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                     (val, torch.float16, "val"), (B, torch.float16, "B")):
+        _need(t, d, nm)
+    m = rowptr.numel() - 1
+    K = B.shape[1]
+    if C is None:
+        C = torch.empty((m, K), dtype=torch.float32, device=B.device)
+    _need(C, torch.float32, "C")
+    if C.shape != (m, K):
+        raise ValueError(f"C must be {(m, K)}, got {tuple(C.shape)}")
+    check(lib().spmm_gespmm_csrmm_f16(m, K, _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(B),
+                                      _ptr(C), c_void_p(torch.cuda.current_stream().cuda_stream)),
+          "spmm_gespmm_csrmm_f16")
     return C
 
 
@@ -654,4 +694,5 @@ class MultiGPU:
 
 
 __all__ = ["coo2csr", "MultiGPU", "csr2bsr", "bsr2csr", "Handle", "hybrid_csrmm", "default_handle", "gespmm_csrmm", "csrmm", "bsrmm", "bsrmm_f16",
+           "csrmm_f16", "gespmm_csrmm_f16",
            "SpmmError", "ORDER_ROW", "ORDER_COL"]
