@@ -82,6 +82,37 @@ spmm_status_t spmm_destroy(spmm_handle_t handle);
 spmm_status_t spmm_set_stream(spmm_handle_t handle, void* stream);
 spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
 
+/* Graph capture. On a handle whose buffers are already large enough a product
+ * queues kernels, memsets and device-to-device copies on the handle's stream
+ * and nothing else, so it can be captured in a HIP graph (hipStreamBeginCapture
+ * on that stream) and replayed: every replay re-reads rowptr / colind / val, B
+ * and C at the captured addresses and returns the handle's tickets, flags and
+ * sums to rest, and gives the bits of the eager call on those operands
+ * (tests/test_gpu_graph_replay.py).
+ *   Capturable, and tested so: spmm_csrmm_ex_f32 / _f16 / _f64 (any
+ *     spmm_set_csr_waves_per_cu), spmm_csrmm_hot_f32, spmm_bsrmm_ex_f32 / _f16
+ *     / _f64 (SPMM_BSR_SMALL_GROUPED included), spmm_hybrid_csrmm_f32 /
+ *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, and the filling call of a group
+ *     analysis. The setters of handle options are host-only: what they set is
+ *     baked into the launches captured after them.
+ *   Not capturable (they hand a size or a flag back to the host, and
+ *     synchronise for it): the analyses that return a size (the size query of
+ *     a group analysis), the device converters (spmm_xcsr2bsr_nnz_dev,
+ *     spmm_scsr2bsr_dev, spmm_sbsr2csr_dev, spmm_xbsr_reblock32_nnzb /
+ *     spmm_sbsr_reblock32), spmm_bsr_small_path and spmm_get_kernel_times.
+ *     Run them before the capture.
+ *   Precondition: one eager call with the same arguments on the same handle
+ *     beforehand (it sizes the handle's buffers), and kernel timing off. A
+ *     call that would have to grow a buffer while the handle's stream is
+ *     capturing returns SPMM_STATUS_NOT_SUPPORTED before it synchronises,
+ *     frees or allocates anything; the capture itself stays valid.
+ *   Lifetime: a graph holds pointers into the handle's buffers. The handle must
+ *     outlive its graphs, and any later call on that handle that grows a buffer
+ *     (a larger shape, another entry) frees what earlier graphs point to:
+ *     capture again after it. The handle-less spmm_gespmm_csrmm_* entries use
+ *     the process-wide default handle, so for them the rule spans every caller
+ *     in the process. */
+
 spmm_status_t spmm_create_mat_descr(spmm_mat_descr_t* descr);
 spmm_status_t spmm_destroy_mat_descr(spmm_mat_descr_t descr);
 spmm_status_t spmm_set_mat_type(spmm_mat_descr_t descr, spmm_matrix_type_t type);

@@ -5,10 +5,20 @@
 
 namespace spmm {
 
+// Growth synchronises the stream, frees and allocates: none of that may happen while
+// the handle's stream is being captured (it would invalidate the capture with an
+// error of the runtime's), so a growing call under capture is refused before any of
+// it. Only the growth paths ask; a query that fails counts as capturing.
+static bool stream_capturing(spmm_context* ctx) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
 static spmm_status_t grow_buffer(spmm_context* ctx, void*& buf, size_t& cap, size_t bytes) {
   if (bytes <= cap) return SPMM_STATUS_SUCCESS;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (bytes <= cap) return SPMM_STATUS_SUCCESS;
+  if (stream_capturing(ctx)) return SPMM_STATUS_NOT_SUPPORTED;
   // The old buffer may still be in use by queued work on this stream.
   if (buf) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -47,6 +57,7 @@ spmm_status_t ensure_order_buffer(spmm_context* ctx, size_t n) {
   if (n <= ctx->order_cap) return SPMM_STATUS_SUCCESS;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n <= ctx->order_cap) return SPMM_STATUS_SUCCESS;
+  if (stream_capturing(ctx)) return SPMM_STATUS_NOT_SUPPORTED;
   if (ctx->order) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return from_hip(e);
@@ -68,6 +79,7 @@ spmm_status_t ensure_tickets(spmm_context* ctx, size_t n) {
   if (n <= ctx->tickets_cap) return SPMM_STATUS_SUCCESS;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n <= ctx->tickets_cap) return SPMM_STATUS_SUCCESS;
+  if (stream_capturing(ctx)) return SPMM_STATUS_NOT_SUPPORTED;
   if (ctx->tickets) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return from_hip(e);

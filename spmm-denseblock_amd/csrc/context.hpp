@@ -104,8 +104,11 @@ struct spmm_context {
 
 namespace spmm {
 
-// Grow the handle workspace to at least `bytes`. Not graph-capture safe on
-// the first (growing) call; steady-state calls never allocate.
+// Grow the handle workspace to at least `bytes`. Steady-state calls never
+// allocate; a growing call synchronises, frees and allocates, so while the
+// handle's stream is capturing it returns SPMM_STATUS_NOT_SUPPORTED instead
+// (all six). Growth frees the old buffer: graphs captured earlier on this
+// handle point into it and must be captured again (include/spmm_hip.h).
 spmm_status_t ensure_workspace(spmm_context* ctx, size_t bytes);
 // The same for the kernel scratch buffer.
 spmm_status_t ensure_scratch(spmm_context* ctx, size_t bytes);

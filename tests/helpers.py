@@ -574,3 +574,84 @@ def cs2_segments_splits(rowptr, ntiles, num_cus=256):
     if lens.max() <= 2 * -(-nnzb // slots):  # rounded up: the stricter reading
         return 0
     return int((lens > L).sum())
+
+
+# ------------------------------------------- graph replay: variants of the step inputs
+# (tests/test_gpu_graph_replay.py writes them over a captured step's operands, in place;
+# tests/test_graph_replay_helpers.py checks on the host that each really differs)
+REPLAY_STRUCTURE_STEPS, REPLAY_VALUE_STEPS = "abldef", "cghk"
+
+
+def reversed_rows(rowptr, colind, val):
+    """The CSR / BSR matrix with its (block) rows in reverse order: rowptr rebuilt from
+    the reversed lengths (same start), colind and val (val.size / colind.size values per
+    entry) concatenated row by row in reverse. Same sizes, same nnz / nnzb."""
+    rowptr = np.asarray(rowptr)
+    m = rowptr.size - 1
+    lens = np.diff(rowptr)[::-1]
+    rp = (rowptr[0] + np.concatenate([[0], np.cumsum(lens)])).astype(rowptr.dtype)
+    take = (np.concatenate([np.arange(rowptr[r], rowptr[r + 1]) for r in range(m - 1, -1, -1)])
+            if m and rowptr[-1] > rowptr[0] else np.zeros(0, np.int64)) - rowptr[0]
+    per = val.size // colind.size if colind.size else 0
+    return (rp, np.ascontiguousarray(colind[take]),
+            np.ascontiguousarray(val.reshape(colind.size, per)[take].reshape(val.shape)))
+
+
+def _like(rng, a):
+    """New contents of a's shape and type from a's own distribution family: uniform(-1, 1)
+    for fp32 / fp16, standard normal for fp64."""
+    if a.dtype == np.float64:
+        return rng.standard_normal(a.shape)
+    return rng.uniform(-1, 1, a.shape).astype(np.float32).astype(a.dtype)
+
+
+def graph_replay_variant(name, I):
+    """Host operands that replace those of reuse step `name` (the keys of
+    tests/test_gpu_handle_reuse.py's input dict I) under a captured graph: the same
+    shapes, nnz / nnzb and dtypes, other contents, from a fixed seed per step.
+
+      a, b, l, d, e, f  the matrix with its (block) rows reversed, a new B and C0
+      c, g, h, k        the same structure with new values, B and C0 (a zero of a BSR
+                        block stays a zero: the hybrid's parts are the divide of the
+                        re-valued matrix)
+      i                 a new B and C0 only (the values live in the analysis buffer)"""
+    rng = np.random.default_rng(9100 + ord(name))
+    new = lambda *keys: {k: _like(rng, I[k]) for k in keys}  # noqa: E731
+    if name == "a":
+        return {"csr": reversed_rows(*I["csr"]), **new("a_B", "a_C0")}
+    if name == "b":
+        return {"csr": reversed_rows(*I["csr"]), **new("b_B")}
+    if name == "l":
+        return {"l_csr": reversed_rows(*I["l_csr"]), **new("l_B")}
+    if name == "d":
+        return {"seg": reversed_rows(*I["seg"]), **new("seg_B")}
+    if name == "e":
+        return {"seg": reversed_rows(*I["seg"]), **new("seg_B", "seg_C0")}
+    if name == "f":
+        out = {}
+        for sb in (8, 2):
+            out[f"small{sb}"] = reversed_rows(*I[f"small{sb}"])
+            out.update(new(f"small{sb}_B", f"small{sb}_C0"))
+        return out
+    if name == "c":
+        rp, ci, v = I["csr"]
+        return {"csr": (rp, ci, _like(rng, v)), **new("b_B")}
+    if name == "g":
+        from spmm_hip import prep
+        rp, ci, v = I["hyb_A"]
+        v = _like(rng, v)
+        return {"hyb_A": (rp, ci, v),
+                "hyb": prep.divide(HYBRID_EX_M, rp, ci, v, 32, HYBRID_EX_DENSITY[32]),
+                **new("hyb_B", "hyb_C0")}
+    if name == "h":
+        rp, ci, v = I["h16"]
+        return {"h16": (rp, ci, _like(rng, v)), **new("h16_B")}
+    if name == "k":
+        out = new("c64_Bt", "c64_C0t", "b64_B", "b64_C0")
+        for key in ("c64", "b64"):
+            rp, ci, v = I[key]
+            out[key] = rp, ci, _like(rng, v)
+        return out
+    if name == "i":
+        return new("g16_B", "g32_B", "g_C0")
+    raise KeyError(name)
