@@ -79,6 +79,33 @@ const char* spmm_get_status_string(spmm_status_t status);
 
 spmm_status_t spmm_create(spmm_handle_t* handle);
 spmm_status_t spmm_destroy(spmm_handle_t handle);
+/* Streams. A handle's device buffers carry one call's state while its kernels
+ * run (split-row tickets and partial sums, staged copies of B and C, segment
+ * lists, probe sums), so the calls of one handle must run one after the other
+ * on the device. On one stream they do. When the stream changes
+ * (spmm_set_stream with another stream, or a handle-less spmm_gespmm_csrmm_*
+ * entry called with a stream other than the default handle's current one), the
+ * library keeps that order itself: the new stream is made to wait for
+ * everything the handle has queued on the old one (an event recorded there)
+ * before any buffer is looked at, grown or freed. Two streams fed through one
+ * handle therefore never overlap; give streams that should run concurrently a
+ * handle each (tests/test_gpu_stream_switch.py).
+ *   Setting the stream the handle already has compares two pointers and queues
+ *     nothing. A handle that owns no device buffer yet (a new one, or one
+ *     whose calls so far have kept nothing in it) has nothing to order and
+ *     just takes the stream.
+ *   Capture: while the old or the new stream is being captured, a change that
+ *     needs the order returns SPMM_STATUS_NOT_SUPPORTED before anything is
+ *     recorded, waited for or synchronised; the handle keeps its old stream
+ *     and the capture stays valid. Bind the handle to the capture stream
+ *     before the capture begins.
+ *   Lifetime: a stream must still exist when the handle next changes away
+ *     from it (the event is recorded on it then). If it does not, the change
+ *     waits for the whole device instead.
+ *   Threads: one host thread at a time drives a handle, and the stream is
+ *     part of that: it is read and written without a lock. This includes the
+ *     process-wide default handle of the handle-less entries, whatever stream
+ *     each caller passes. */
 spmm_status_t spmm_set_stream(spmm_handle_t handle, void* stream);
 spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
 
@@ -105,7 +132,11 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *     beforehand (it sizes the handle's buffers), and kernel timing off. A
  *     call that would have to grow a buffer while the handle's stream is
  *     capturing returns SPMM_STATUS_NOT_SUPPORTED before it synchronises,
- *     frees or allocates anything; the capture itself stays valid.
+ *     frees or allocates anything; the capture itself stays valid. The
+ *     handle is on the capture stream before the capture begins: setting
+ *     that same stream again inside the capture adds nothing to the graph,
+ *     while a change of stream on a handle that owns buffers is refused in
+ *     the same way ("Streams" above).
  *   Lifetime: a graph holds pointers into the handle's buffers. The handle must
  *     outlive its graphs, and any later call on that handle that grows a buffer
  *     (a larger shape, another entry) frees what earlier graphs point to:

@@ -121,7 +121,8 @@ spmm_status_t spmm_gespmm_csrmm_f32(int A_nrows, int B_ncols, const int* A_rowPt
   if (!A_rowPtr || !A_colInd || !A_val || !B || !C) return SPMM_STATUS_INVALID_VALUE;
   spmm_context* ctx = default_context();
   if (!ctx) return SPMM_STATUS_NOT_INITIALIZED;
-  ctx->stream = reinterpret_cast<hipStream_t>(stream);
+  const spmm_status_t sw = switch_stream(ctx, reinterpret_cast<hipStream_t>(stream));
+  if (sw != SPMM_STATUS_SUCCESS) return sw;
   // nnz is only known on the device (A_rowPtr[A_nrows]); -1 sizes the grid
   // from the row count.
   return csrmm_impl(ctx, A_nrows, B_ncols, A_nrows, -1, 1.f, A_rowPtr, A_colInd, A_val, 0, B,
@@ -158,7 +159,8 @@ spmm_status_t spmm_gespmm_csrmm_f16(int A_nrows, int B_ncols, const int* A_rowPt
   if (!A_rowPtr || !A_colInd || !A_val || !B || !C) return SPMM_STATUS_INVALID_VALUE;
   spmm_context* ctx = default_context();
   if (!ctx) return SPMM_STATUS_NOT_INITIALIZED;
-  ctx->stream = reinterpret_cast<hipStream_t>(stream);
+  const spmm_status_t sw = switch_stream(ctx, reinterpret_cast<hipStream_t>(stream));
+  if (sw != SPMM_STATUS_SUCCESS) return sw;
   return csrmm_impl(ctx, A_nrows, B_ncols, A_nrows, -1, 1.f, A_rowPtr, A_colInd, A_val, 0, B,
                     B_ncols, SPMM_ORDER_ROW, 0.f, C, B_ncols, SPMM_ORDER_ROW);
 }
@@ -433,12 +435,16 @@ spmm_status_t spmm_gespmm_csrmm_f64(int A_nrows, int B_ncols, const int* A_rowPt
   if (A_nrows < 0 || B_ncols < 0) return SPMM_STATUS_INVALID_VALUE;
   if (A_nrows == 0 || B_ncols == 0) return SPMM_STATUS_SUCCESS;
   if (!A_rowPtr || !C || !B) return SPMM_STATUS_INVALID_VALUE;
+  // The fp64 kernel keeps nothing in the handle, and the default handle goes back to
+  // the stream of its fp32 / fp16 callers: both changes go through switch_stream, so a
+  // handle with buffers orders `stream` behind its own and its own behind this product.
   hipStream_t saved = ctx->stream;
-  ctx->stream = reinterpret_cast<hipStream_t>(stream);
+  const spmm_status_t sw = switch_stream(ctx, reinterpret_cast<hipStream_t>(stream));
+  if (sw != SPMM_STATUS_SUCCESS) return sw;
   const spmm_status_t st = launch_csrmm_f64(ctx, A_nrows, B_ncols, A_rowPtr, A_colInd, A_val, 0,
                                             B, B_ncols, true, 1.0, 0.0, C, B_ncols, true);
-  ctx->stream = saved;
-  return st;
+  const spmm_status_t back = switch_stream(ctx, saved);
+  return st != SPMM_STATUS_SUCCESS ? st : back;
 }
 
 spmm_status_t spmm_bsrmm_ex_f64(spmm_handle_t handle, spmm_direction_t dir, int mb, int kb, int n,

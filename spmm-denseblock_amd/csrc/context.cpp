@@ -14,12 +14,16 @@ static bool stream_capturing(spmm_context* ctx) {
   return hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 
+// The old buffer may be in use by work queued on the handle's current stream and, if
+// the stream has changed, on earlier ones. switch_stream ordered the current stream
+// behind those at the moment of each change, before any buffer was looked at, so the
+// one synchronise of ctx->stream below (and in the order and ticket growth paths)
+// covers them all before the buffer is freed.
 static spmm_status_t grow_buffer(spmm_context* ctx, void*& buf, size_t& cap, size_t bytes) {
   if (bytes <= cap) return SPMM_STATUS_SUCCESS;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (bytes <= cap) return SPMM_STATUS_SUCCESS;
   if (stream_capturing(ctx)) return SPMM_STATUS_NOT_SUPPORTED;
-  // The old buffer may still be in use by queued work on this stream.
   if (buf) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return from_hip(e);
@@ -134,6 +138,52 @@ static spmm_context* make_context() {
   return ctx;
 }
 
+spmm_status_t switch_stream(spmm_context* ctx, hipStream_t to) {
+  if (to == ctx->stream) return SPMM_STATUS_SUCCESS;
+  // Every device state that outlives a launch sits in one of these; a handle that has
+  // none (spmm_create followed by spmm_set_stream) has queued nothing to wait for.
+  const bool owns = ctx->ws || ctx->scratch || ctx->stage || ctx->order || ctx->tickets ||
+                    ctx->grp_pend || ctx->grp_cols;
+  if (owns) {
+    // Under capture an order would become part of the graph, or invalidate it: refused
+    // before anything else happens, like growth. A query that fails on `to` counts as
+    // capturing, and so does one that fails on the old stream with an error of the
+    // capture family (the legacy stream while a capture elsewhere forbids touching it);
+    // any other failure there means that the old stream is gone.
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(to, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      return SPMM_STATUS_NOT_SUPPORTED;
+    hipError_t e = hipStreamIsCapturing(ctx->stream, &cs);
+    if (e == hipSuccess ? cs != hipStreamCaptureStatusNone
+                        : e >= hipErrorStreamCaptureUnsupported &&
+                              e <= hipErrorStreamCaptureWrongThread)
+      return SPMM_STATUS_NOT_SUPPORTED;
+    if (e == hipSuccess && !ctx->switch_ev) {
+      e = hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming);
+      if (e != hipSuccess) {
+        ctx->switch_ev = nullptr;
+        return from_hip(e);
+      }
+    }
+    // All earlier work of the handle has been queued by now (one host thread drives it).
+    if (e == hipSuccess) e = hipEventRecord(ctx->switch_ev, ctx->stream);
+    if (e == hipSuccess) {
+      e = hipStreamWaitEvent(to, ctx->switch_ev, 0);
+      if (e != hipSuccess) return from_hip(e);
+    } else {
+      // The old stream no longer exists (the header asks callers to keep it until the
+      // handle has left it): nothing can be recorded on it, so wait for the whole
+      // device; neither stream is capturing here. No GPU test destroys a stream under
+      // the library, so this path is covered by reading alone.
+      (void)hipGetLastError();
+      e = hipDeviceSynchronize();
+      if (e != hipSuccess) return from_hip(e);
+    }
+  }
+  ctx->stream = to;
+  return SPMM_STATUS_SUCCESS;
+}
+
 spmm_context* default_context() {
   // One default handle per device, created on first use.
   static std::mutex mu;
@@ -195,14 +245,14 @@ spmm_status_t spmm_destroy(spmm_handle_t h) {
   if (h->order) (void)hipFree(h->order);
   for (auto e : h->ev_start) (void)hipEventDestroy(e);
   for (auto e : h->ev_stop) (void)hipEventDestroy(e);
+  if (h->switch_ev) (void)hipEventDestroy(h->switch_ev);
   delete h;
   return SPMM_STATUS_SUCCESS;
 }
 
 spmm_status_t spmm_set_stream(spmm_handle_t h, void* stream) {
   if (!h) return SPMM_STATUS_NOT_INITIALIZED;
-  h->stream = reinterpret_cast<hipStream_t>(stream);
-  return SPMM_STATUS_SUCCESS;
+  return switch_stream(h, reinterpret_cast<hipStream_t>(stream));
 }
 
 spmm_status_t spmm_get_stream(spmm_handle_t h, void** stream) {

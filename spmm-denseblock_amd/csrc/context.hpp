@@ -24,7 +24,12 @@ struct spmm_mat_descr {
 };
 
 struct spmm_context {
+  // Written by spmm::switch_stream alone (and by no lock: one host thread at a time
+  // drives a handle, the default handle included).
   hipStream_t stream = nullptr;
+  // Orders a new stream behind the old one when the stream changes (switch_stream):
+  // created at the first such change, timing disabled, destroyed in spmm_destroy.
+  hipEvent_t switch_ev = nullptr;
   int device = 0;
   int num_cus = 256;
   int csr_waves_per_cu = 0;  // 0 = default
@@ -128,6 +133,19 @@ void timing_end(spmm_context* ctx, int slot);
 
 // Process-wide default handle for the handle-less gespmm entry point.
 spmm_context* default_context();
+
+// The one way a handle's stream changes (spmm_set_stream and the handle-less entries,
+// which run on the default handle). The same stream again: a pointer compare, nothing
+// is queued. Another stream: `to` is first ordered behind everything the handle has
+// queued on its old stream (the handle's event, recorded there and waited for on `to`),
+// because the handle's buffers carry one call's state while its kernels run (split-row
+// tickets and piece slots, staged B and C, segment lists, probe sums): two calls on two
+// unordered streams would share them. A handle that owns no device buffer yet has
+// queued nothing that a later call could disturb and switches without an order. While
+// the old or the new stream is capturing, a switch that needs an order returns
+// SPMM_STATUS_NOT_SUPPORTED before anything is recorded, waited for or synchronised,
+// and the handle keeps its stream.
+spmm_status_t switch_stream(spmm_context* ctx, hipStream_t to);
 
 inline spmm_status_t from_hip(hipError_t e) {
   if (e == hipSuccess) return SPMM_STATUS_SUCCESS;

@@ -50,8 +50,11 @@ class Handle:
         return self._h
 
     def set_stream(self, stream: torch.cuda.Stream) -> None:
-        self.stream = stream
+        """spmm_set_stream: another stream is first ordered behind what the handle has
+        queued on its old one; refused (SpmmError, NOT_SUPPORTED; the handle keeps its
+        stream) while either of the two is being captured."""
         check(lib().spmm_set_stream(self._h, c_void_p(stream.cuda_stream)), "spmm_set_stream")
+        self.stream = stream
 
     def set_timing(self, enable: bool) -> None:
         check(lib().spmm_set_kernel_timing(self._h, int(enable)), "spmm_set_kernel_timing")
@@ -102,6 +105,9 @@ _handles: dict[int, Handle] = {}
 
 
 def default_handle() -> Handle:
+    """The device's shared handle, rebound to torch's current stream on every call: a
+    call under another torch.cuda.stream(...) block runs behind the handle's earlier ones
+    (Handle.set_stream); give concurrent streams a Handle each."""
     dev = torch.cuda.current_device()
     h = _handles.get(dev)
     if h is None:

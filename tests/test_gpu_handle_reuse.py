@@ -14,9 +14,10 @@ first of those results is held to the step's oracle with the bar of the entry's 
 test (two equal wrong answers must not pass). Then the steps run in sequence on one
 handle, forward (with a, d, f once more at the end: a small request after large ones),
 backward, and forward on a handle bound to a side stream from its creation; each
-result is compared bit for bit with the fresh handle's. No stream change inside a
-sequence, one handle at a time, every call eager: tests/test_gpu_graph_replay.py
-captures the same steps and replays them.
+result is compared bit for bit with the fresh handle's. A handle whose stream changes
+between calls is tests/test_gpu_stream_switch.py's subject; here one handle at a time,
+every call eager: tests/test_gpu_graph_replay.py captures the same steps and replays
+them.
 
   a  CSR, n = 256, column-major B and C, one hub row of 40,000 nonzeros: split rows
      (tickets, piece slots in ws) and both staging areas of ws
