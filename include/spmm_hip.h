@@ -126,8 +126,10 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *     synchronise for it): the analyses that return a size (the size query of
  *     a group analysis), the device converters (spmm_xcsr2bsr_nnz_dev,
  *     spmm_scsr2bsr_dev, spmm_sbsr2csr_dev, spmm_xbsr_reblock32_nnzb /
- *     spmm_sbsr_reblock32), spmm_bsr_small_path and spmm_get_kernel_times.
- *     Run them before the capture.
+ *     spmm_sbsr_reblock32, spmm_csr2csc_dev), spmm_bsr_small_path and
+ *     spmm_get_kernel_times. Run them before the capture. spmm_csr2csc_dev
+ *     checks for a capture itself and returns SPMM_STATUS_NOT_SUPPORTED
+ *     before it queues anything.
  *   Precondition: one eager call with the same arguments on the same handle
  *     beforehand (it sizes the handle's buffers), and kernel timing off. A
  *     call that would have to grow a buffer while the handle's stream is
@@ -236,7 +238,10 @@ spmm_status_t spmm_gespmm_csrmm_f32(int A_nrows, int B_ncols, const int* A_rowPt
 
 /* Drop-in for cusparseScsrmm (run_csrmm.cu:135-137):
  *   C(m x n, col-major, ldc) = alpha*op(A)(m x k) * B(k x n, col-major, ldb) + beta*C.
- * Only transA = NON_TRANSPOSE is supported (as in the reference call sites). */
+ * Only transA = NON_TRANSPOSE is supported (as in the reference call sites);
+ * anything else returns SPMM_STATUS_MATRIX_TYPE_NOT_SUPPORTED, here and in
+ * spmm_scsrmm2, spmm_dcsrmm2, spmm_sbsrmm and spmm_dbsrmm. For a transposed
+ * product, build A^T once with spmm_csr2csc_dev and multiply by that. */
 spmm_status_t spmm_scsrmm(spmm_handle_t handle, spmm_operation_t transA, int m, int n, int k,
                           int nnz, const float* alpha, const spmm_mat_descr_t descrA,
                           const float* csrValA, const int* csrRowPtrA, const int* csrColIndA,
@@ -244,7 +249,8 @@ spmm_status_t spmm_scsrmm(spmm_handle_t handle, spmm_operation_t transA, int m, 
 
 /* Drop-in for cusparseScsrmm2 (run_csrmm.cu:139-142, test_csrmm.cu:126-129):
  *   transB = NON_TRANSPOSE: B col-major k x n (ldb >= k);
- *   transB = TRANSPOSE:     B row-major k x n (ldb >= n);  C col-major. */
+ *   transB = TRANSPOSE:     B row-major k x n (ldb >= n);  C col-major.
+ * transA = NON_TRANSPOSE only; for A^T build it once with spmm_csr2csc_dev. */
 spmm_status_t spmm_scsrmm2(spmm_handle_t handle, spmm_operation_t transA,
                            spmm_operation_t transB, int m, int n, int k, int nnz,
                            const float* alpha, const spmm_mat_descr_t descrA,
@@ -324,7 +330,8 @@ spmm_status_t spmm_csrmm_hot_f32(spmm_handle_t handle, int m, int n, int k, int 
  * Status behaviour follows rocsparse_bsrmm.h:109-176 (NOT_INITIALIZED for a
  * null handle, INVALID_VALUE for null descr / negative sizes / null pointers /
  * bad ld, MATRIX_TYPE_NOT_SUPPORTED for transA != N or a bad transB, SUCCESS
- * quick return when mb, n, kb or nnzb is 0). */
+ * quick return when mb, n, kb or nnzb is 0). For a transposed A, transpose the
+ * CSR form once with spmm_csr2csc_dev and convert that (spmm_scsr2bsr_dev). */
 spmm_status_t spmm_sbsrmm(spmm_handle_t handle, spmm_direction_t dir,
                           spmm_operation_t transA, spmm_operation_t transB, int mb, int n,
                           int kb, int nnzb, const float* alpha, const spmm_mat_descr_t descrA,
@@ -536,6 +543,33 @@ spmm_status_t spmm_scsr2bsr(spmm_direction_t dir, int m, int n, const float* csr
                             const int* csrRowPtr, const int* csrColInd, int blockDim,
                             const int* bsrRowPtr, float* bsrVal, int* bsrColInd);
 
+/* CSR -> CSC, that is the CSR form of A^T (n x m); no reference counterpart.
+ *   Input: csrRowPtr[m + 1], csrColInd, csrVal in baseA; nnz = csrRowPtr[m] -
+ *     csrRowPtr[0]. csrRowPtr[0] need not be the base (a view into a larger
+ *     matrix): position p is index p of csrColInd / csrVal as passed, and the
+ *     matrix holds the positions from csrRowPtr[0] - baseA on. Rows need not be
+ *     sorted by column.
+ *   Output: cscColPtr[n + 1] (cscColPtr[0] = baseC, cscColPtr[n] = nnz + baseC,
+ *     a column without entries repeats the pointer), cscRowInd[nnz] in baseC,
+ *     cscVal[nnz] and, when perm is not NULL, perm[nnz] = the CSR position of
+ *     each CSC entry (0-based; cscVal = csrVal[perm] refreshes the values of a
+ *     matrix whose pattern stays). Inside a column the entries are in ascending
+ *     CSR position (ascending row; duplicate (row, col) entries keep their CSR
+ *     order): the stable sort of the positions by column, so every output byte
+ *     is a function of the input alone, and the output's rows are sorted by
+ *     column whatever the input's were.
+ *   valueBytes = 0 (pattern only; csrVal / cscVal may be NULL), 2, 4 or 8: the
+ *     values are moved as opaque words (binary16, fp32, fp64).
+ *   Input and output arrays must not overlap.
+ *   SPMM_STATUS_INVALID_VALUE: a negative size, another valueBytes or base, a
+ *     needed pointer that is NULL, a decreasing row pointer, csrRowPtr[0] below
+ *     baseA, an nnz other than the row pointer's, a column outside [0, n).
+ * Host pointers, worker threads like the other host conversions. */
+spmm_status_t spmm_csr2csc(int m, int n, int nnz, const void* csrVal, const int* csrRowPtr,
+                           const int* csrColInd, int valueBytes, spmm_index_base_t baseA,
+                           spmm_index_base_t baseC, void* cscVal, int* cscColPtr,
+                           int* cscRowInd, int* perm);
+
 /* cusparseSbsr2csr semantics (bsr2csr.cu:177-188): every block expanded,
  * explicit zeros kept: nnz = nnzb*bs*bs, csrRowPtr[mb*bs+1]. */
 spmm_status_t spmm_sbsr2csr(spmm_direction_t dir, int mb, int nb, const float* bsrVal,
@@ -591,6 +625,38 @@ spmm_status_t spmm_sbsr2csr_dev(spmm_handle_t handle, spmm_direction_t dir, int 
                                 const spmm_mat_descr_t descrC, float* csrVal, int* csrRowPtr,
                                 int* csrColInd);
 
+/* spmm_csr2csc on the device: the contract of spmm_csr2csc above, bit for bit
+ * (tests/test_gpu_csr2csc.py), device pointers, the handle's stream, the index
+ * bases from the descriptors. A column-count histogram (integer atomics: a
+ * count does not depend on arrival order), then a stable LSD radix sort of the
+ * positions by column in ceil(bits(n - 1) / 8) passes of 8-bit digits whose
+ * ranks come from ballots and scans, never from an atomic, then one gather of
+ * rows (written out per position once) and values: no per-column work, so a hub column
+ * costs what its entries cost anywhere else.
+ *   Checks, in order: a NULL handle is SPMM_STATUS_NOT_INITIALIZED; then the
+ *     host-side SPMM_STATUS_INVALID_VALUE cases of spmm_csr2csc that need no
+ *     data (sizes, valueBytes, NULL descriptors or pointers, nnz > 0 with
+ *     n = 0); under stream capture SPMM_STATUS_NOT_SUPPORTED before anything
+ *     is queued; nnz = 0 fills cscColPtr with baseC and returns.
+ *   A column outside [0, n), a decreasing row pointer or an nnz other than the
+ *     row pointer's is found on the device (such an entry is skipped, never
+ *     used as an index) and reported as SPMM_STATUS_INVALID_VALUE after the
+ *     call's one synchronisation, before anything is sorted; the outputs are
+ *     then unspecified. Because of that read-back the call cannot be captured.
+ *   Workspace: from the handle (a steady-state repeat allocates nothing): 4 n
+ *     bytes of column counts plus at most 20.25 bytes per nonzero: 4 for the
+ *     row of every position, 0.25 for the tile counts and their scan, and two
+ *     key and two position buffers of 4 each from three passes on (n > 65 536).
+ *     Two passes: 16.25, 12.25 with perm (the last pass writes into it); one
+ *     pass: 8.25, 4.25 with perm; n <= 1: 4. With kernel timing on, every
+ *     kernel of the call is timed: count, scan, then (digit count, scan,
+ *     scatter) per pass, then the row expansion and the gather. */
+spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
+                               const spmm_mat_descr_t descrA, const void* csrVal,
+                               const int* csrRowPtr, const int* csrColInd, int valueBytes,
+                               const spmm_mat_descr_t descrC, void* cscVal, int* cscColPtr,
+                               int* cscRowInd, int* perm);
+
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's
  * stream). Row indices and the output are in idxBase, as in cuSPARSE:
@@ -627,7 +693,7 @@ spmm_status_t spmm_csrmm_ex_f64(spmm_handle_t handle, int m, int n, int k, int n
                                 spmm_index_base_t base, const double* B, int ldb,
                                 spmm_order_t orderB, double beta, double* C, int ldc,
                                 spmm_order_t orderC);
-/* cusparseDcsrmm2 */
+/* cusparseDcsrmm2 (transA = NON_TRANSPOSE only; A^T: spmm_csr2csc_dev with valueBytes 8) */
 spmm_status_t spmm_dcsrmm2(spmm_handle_t handle, spmm_operation_t transA,
                            spmm_operation_t transB, int m, int n, int k, int nnz,
                            const double* alpha, const spmm_mat_descr_t descrA,
@@ -638,7 +704,8 @@ spmm_status_t spmm_bsrmm_ex_f64(spmm_handle_t handle, spmm_direction_t dir, int 
                                 const int* bsrColInd, const double* bsrVal, const double* B,
                                 int ldb, spmm_order_t orderB, double beta, double* C, int ldc,
                                 spmm_order_t orderC);
-/* cusparseDbsrmm / rocsparse_bsrmm_template<double> */
+/* cusparseDbsrmm / rocsparse_bsrmm_template<double> (transA = NON_TRANSPOSE only; for A^T
+ * transpose the CSR form with spmm_csr2csc_dev before it is blocked) */
 spmm_status_t spmm_dbsrmm(spmm_handle_t handle, spmm_direction_t dir, spmm_operation_t transA,
                           spmm_operation_t transB, int mb, int n, int kb, int nnzb,
                           const double* alpha, const spmm_mat_descr_t descrA,

@@ -233,10 +233,10 @@ spmm_status_t launch_grp_mask16(spmm_context* ctx, spmm_direction_t dir, int nnz
                                 const uint16_t* val, unsigned* masks);
 // stats[0] = max over maxj[0..n), stats[1] = 1 if any maxj is INT_MIN (pass 1's "bad")
 spmm_status_t launch_grp_stats(spmm_context* ctx, const int* maxj, int n, int* stats);
-// exclusive scan of count[0..n) into out[0..n] (out[0] = 0) and *total (one workgroup,
-// convert_kernels.hip)
+// exclusive scan of count[0..n) into out[0..n] (out[0] = base, every entry + base) and
+// *total (the sum without the base; one workgroup, convert_kernels.hip)
 spmm_status_t launch_scan_counts(spmm_context* ctx, const int* count, int n, int* out,
-                                 long long* total);
+                                 long long* total, int base = 0);
 // the grouped bs 32 stream (row-major B and C)
 spmm_status_t launch_bsr32_grp_fill(spmm_context* ctx, long long nitems, int W, spmm_direction_t dir,
                                     const int* rows, const int* src, const float* val,

@@ -297,8 +297,8 @@ __global__ __launch_bounds__(256) void reblock32_values_kernel(long long total, 
 namespace spmm {
 
 spmm_status_t launch_scan_counts(spmm_context* ctx, const int* count, int n, int* out,
-                                 long long* total) {
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, count, n, 0, out, total);
+                                 long long* total, int base) {
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, count, n, base, out, total);
   return from_hip(hipGetLastError());
 }
 

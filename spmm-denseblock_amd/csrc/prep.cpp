@@ -205,6 +205,87 @@ spmm_status_t spmm_csr_partition_rows(int m, const int* csrRowPtr, int nparts, i
   return SPMM_STATUS_SUCCESS;
 }
 
+// CSR -> CSC: the stable counting sort of the CSR positions by column (no reference
+// counterpart; the device form, spmm_csr2csc_dev, is compared against this one). The
+// column counts are integer atomics (order-independent), the column pointer a sequential
+// prefix sum; the fill gives every worker a range of columns holding about nnz / workers
+// entries, and each worker walks all entries in CSR order and places those of its own
+// columns, so the order inside a column is the CSR order whatever the worker count.
+spmm_status_t spmm_csr2csc(int m, int n, int nnz, const void* csrVal, const int* csrRowPtr,
+                           const int* csrColInd, int valueBytes, spmm_index_base_t baseA,
+                           spmm_index_base_t baseC, void* cscVal, int* cscColPtr,
+                           int* cscRowInd, int* perm) {
+  if (m < 0 || n < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (valueBytes != 0 && valueBytes != 2 && valueBytes != 4 && valueBytes != 8)
+    return SPMM_STATUS_INVALID_VALUE;
+  if ((baseA != SPMM_INDEX_BASE_ZERO && baseA != SPMM_INDEX_BASE_ONE) ||
+      (baseC != SPMM_INDEX_BASE_ZERO && baseC != SPMM_INDEX_BASE_ONE))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (!csrRowPtr || !cscColPtr) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrColInd || !cscRowInd || (valueBytes > 0 && (!csrVal || !cscVal))))
+    return SPMM_STATUS_INVALID_VALUE;
+  const int ba = (int)baseA, bc = (int)baseC;
+  const int64_t p0 = (int64_t)csrRowPtr[0] - ba;
+  if (p0 < 0 || (int64_t)csrRowPtr[m] - csrRowPtr[0] != nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (csrRowPtr[r + 1] < csrRowPtr[r]) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  std::vector<int> cnt((size_t)n + 1, 0);  // cnt[c + 1]: entries of column c, then cursors
+  spmm_host::parallel_for(nnz, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const int c = csrColInd[p0 + i] - ba;
+      if (c < 0 || c >= n) {
+        ok = false;
+        return;
+      }
+      __atomic_fetch_add(&cnt[(size_t)c + 1], 1, __ATOMIC_RELAXED);
+    }
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  cscColPtr[0] = bc;
+  int64_t acc = 0;
+  for (int c = 0; c < n; ++c) {
+    const int here = cnt[(size_t)c + 1];
+    cnt[(size_t)c + 1] = (int)acc;  // cursor of column c (cnt[0] stays unused)
+    acc += here;
+    cscColPtr[c + 1] = (int)(acc + bc);
+  }
+  if (nnz == 0) return SPMM_STATUS_SUCCESS;
+  const int nt = (int)std::min<int64_t>(spmm_host::num_threads(), std::max<int64_t>(1, nnz / 65536));
+  // worker t owns the columns [cut[t], cut[t + 1]): cuts at equal shares of the entries
+  std::vector<int> cut((size_t)nt + 1, n);
+  cut[0] = 0;
+  for (int t = 1; t < nt; ++t) {
+    const int64_t target = (int64_t)nnz * t / nt + bc;
+    cut[t] = (int)(std::lower_bound(cscColPtr, cscColPtr + n, (int)target) - cscColPtr);
+  }
+  auto fill = [&](int clo, int chi) {
+    for (int r = 0; r < m; ++r)
+      for (int64_t p = (int64_t)csrRowPtr[r] - ba; p < (int64_t)csrRowPtr[r + 1] - ba; ++p) {
+        const int c = csrColInd[p] - ba;
+        if (c < clo || c >= chi) continue;
+        const size_t dst = (size_t)cnt[(size_t)c + 1]++;
+        cscRowInd[dst] = r + bc;
+        if (perm) perm[dst] = (int)p;
+        if (valueBytes)
+          std::memcpy(static_cast<char*>(cscVal) + dst * valueBytes,
+                      static_cast<const char*>(csrVal) + (size_t)p * valueBytes, valueBytes);
+      }
+  };
+  if (nt <= 1) {
+    fill(0, n);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+      if (cut[t] < cut[t + 1]) th.emplace_back(fill, cut[t], cut[t + 1]);
+    for (auto& x : th) x.join();
+  }
+  return SPMM_STATUS_SUCCESS;
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------

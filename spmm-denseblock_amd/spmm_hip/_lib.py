@@ -125,6 +125,8 @@ _PROTOS = {
     "spmm_xcsr2bsr_nnz": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _PI]),
     "spmm_scsr2bsr": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "spmm_sbsr2csr": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "spmm_csr2csc": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P,
+                             _P]),
     "spmm_calculate_nnzb": (c_int64, [c_int, _P, _P, c_int]),
     "spmm_csr_partition_rows": (c_int, [c_int, _P, c_int, _P]),
     "spmm_divide_nnz": (c_int, [c_int, _P, _P, c_int, c_float, _P, _P, _PI, _PI]),
@@ -137,6 +139,8 @@ _PROTOS = {
                                   _P]),
     "spmm_sbsr2csr_dev": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P,
                                   _P]),
+    "spmm_csr2csc_dev": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P,
+                                 _P]),
     "spmm_xcoo2csr": (c_int, [_P, _P, c_int, c_int, _P, c_int]),
     # spmm_multi.h
     "spmm_multi_create": (c_int, [POINTER(c_void_p), c_int, _P]),

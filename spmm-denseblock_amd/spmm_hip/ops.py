@@ -549,6 +549,56 @@ def csr2bsr(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, *, m:
     return brp, bci, bval
 
 
+_VALUE_BYTES = {torch.float16: 2, torch.float32: 4, torch.float64: 8}
+
+
+def csr2csc(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor | None = None, *,
+            m: int, n: int, base: int = 0, base_out: int | None = None,
+            return_perm: bool = False, nnz: int | None = None,
+            handle: Handle | None = None):
+    """Device CSR -> CSC (spmm_csr2csc_dev): the CSR arrays of the transposed n x m
+    matrix, entries of a column in CSR order, so its rows are sorted by column and
+    every byte is a function of the input alone. val: float16, float32, float64 or
+    None (pattern only). rowptr[0] may exceed `base` (rowptr[i:j + 1] of a larger
+    matrix with its full colind / val). nnz: read from the row pointer when not given.
+    Returns (colptr, rowind[, val][, perm]) in `base_out` (default: `base`); perm holds
+    the position in colind / val of each output entry (val_t = val[perm.long()]).
+    Synchronises once; not capturable."""
+    _need(rowptr, torch.int32, "rowptr")
+    _need(colind, torch.int32, "colind")
+    vb = 0
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype not in _VALUE_BYTES:
+            raise TypeError("val must be a float16, float32 or float64 tensor or None")
+        _need(val, val.dtype, "val")
+        vb = _VALUE_BYTES[val.dtype]
+    if rowptr.numel() < m + 1:
+        raise ValueError(f"csr2csc: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    if nnz is None:
+        ends = rowptr[[0, m]].tolist()
+        nnz = ends[1] - ends[0]
+        if nnz < 0 or colind.numel() < ends[1] - base or ends[0] < base:
+            raise ValueError("csr2csc: the row pointer does not fit colind")
+    if val is not None and val.numel() < colind.numel():
+        raise ValueError("csr2csc: val is shorter than colind")
+    h = handle or default_handle()
+    da, dc = _Descr(base), _Descr(base if base_out is None else base_out)
+    dev = rowptr.device
+    colptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    rowind = torch.empty(nnz, dtype=torch.int32, device=dev)
+    cval = None if val is None else torch.empty(nnz, dtype=val.dtype, device=dev)
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev) if return_perm else None
+    check(lib().spmm_csr2csc_dev(h.raw, m, n, nnz, da.raw, _ptr(val), _ptr(rowptr), _ptr(colind),
+                                 vb, dc.raw, _ptr(cval), _ptr(colptr), _ptr(rowind), _ptr(perm)),
+          "spmm_csr2csc_dev")
+    out = (colptr, rowind)
+    if val is not None:
+        out += (cval,)
+    if return_perm:
+        out += (perm,)
+    return out
+
+
 def bsr_reblock32(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, *, mb: int,
                   bs: int, direction: int = DIRECTION_ROW, handle: Handle | None = None):
     """The same BSR matrix in 32 x 32 blocks (spmm_xbsr_reblock32_nnzb +
@@ -699,6 +749,6 @@ class MultiGPU:
             pass
 
 
-__all__ = ["coo2csr", "MultiGPU", "csr2bsr", "bsr2csr", "Handle", "hybrid_csrmm", "default_handle", "gespmm_csrmm", "csrmm", "bsrmm", "bsrmm_f16",
+__all__ = ["coo2csr", "MultiGPU", "csr2bsr", "csr2csc", "bsr2csr", "Handle", "hybrid_csrmm", "default_handle", "gespmm_csrmm", "csrmm", "bsrmm", "bsrmm_f16",
            "csrmm_f16", "gespmm_csrmm_f16",
            "SpmmError", "ORDER_ROW", "ORDER_COL"]

@@ -1,7 +1,7 @@
 """Host-side preprocessing and data feeders (numpy in, numpy out).
 
 Thin wrappers over the C ABI of libspmm_hip.so:
-  csr2bsr / bsr2csr / calculate_nnzb / partition_rows   (include/spmm_hip.h)
+  csr2bsr / bsr2csr / csr2csc / calculate_nnzb / partition_rows   (include/spmm_hip.h)
   rng_seed / random_array / random_csr / random_bsr /
   load_csr / dump_csr / load_graph / save_csr_bin / load_csr_bin / load_csr_cached /
   powerlaw_csr / community_csr                                  (include/spmm_host.h)
@@ -72,6 +72,45 @@ def bsr2csr(mb: int, nb: int, rowptr, colind, val, bs: int, direction: int = 0):
     check(lib().spmm_sbsr2csr(direction, mb, nb, _p(val), _p(rowptr), _p(colind), bs, _p(v),
                               _p(rp), _p(ci)), "spmm_sbsr2csr")
     return rp, ci, v
+
+
+_VALUE_DTYPES = (np.float16, np.float32, np.float64)
+
+
+def csr2csc(m: int, n: int, rowptr, colind, val=None, *, base: int = 0,
+            base_out: int | None = None, return_perm: bool = False):
+    """spmm_csr2csc: the CSC form of the m x n CSR matrix, that is the CSR form of its
+    transpose, entries of a column in CSR order (the stable sort of the positions by
+    column). val: float16 / float32 / float64 (moved as bits) or None (pattern only).
+    rowptr[0] may exceed `base` (a view: rowptr[i:j + 1] with the full colind / val).
+    Returns (colptr[n+1], rowind[nnz][, val[nnz]][, perm[nnz]]) in `base_out` (default:
+    `base`); perm holds the CSR position of each CSC entry."""
+    rowptr, colind = _i32(rowptr), _i32(colind)
+    if rowptr.size != m + 1:
+        raise ValueError(f"csr2csc: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    vb = 0
+    if val is not None:
+        val = np.ascontiguousarray(val)
+        if val.dtype not in _VALUE_DTYPES:
+            raise TypeError(f"csr2csc: val must be float16, float32 or float64, got {val.dtype}")
+        vb = val.dtype.itemsize
+    nnz = int(rowptr[m]) - int(rowptr[0])
+    last = int(rowptr[m]) - base
+    if nnz < 0 or colind.size < last or (val is not None and val.size < last):
+        raise ValueError("csr2csc: colind / val are shorter than the row pointer says")
+    base_out = base if base_out is None else base_out
+    colptr = np.zeros(n + 1, dtype=np.int32)
+    rowind = np.zeros(nnz, dtype=np.int32)
+    cval = None if val is None else np.zeros(nnz, dtype=val.dtype)
+    perm = np.zeros(nnz, dtype=np.int32) if return_perm else None
+    check(lib().spmm_csr2csc(m, n, nnz, _p(val), _p(rowptr), _p(colind), vb, base, base_out,
+                             _p(cval), _p(colptr), _p(rowind), _p(perm)), "spmm_csr2csc")
+    out = (colptr, rowind)
+    if val is not None:
+        out += (cval,)
+    if return_perm:
+        out += (perm,)
+    return out
 
 
 def calculate_nnzb(n: int, rowptr, colind, bs: int) -> int:
