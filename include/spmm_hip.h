@@ -119,7 +119,8 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *   Capturable, and tested so: spmm_csrmm_ex_f32 / _f16 / _f64 (any
  *     spmm_set_csr_waves_per_cu), spmm_csrmm_hot_f32, spmm_bsrmm_ex_f32 / _f16
  *     / _f64 (SPMM_BSR_SMALL_GROUPED included), spmm_hybrid_csrmm_f32 /
- *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, and the filling call of a group
+ *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 (which keeps
+ *     nothing in the handle's buffers), and the filling call of a group
  *     analysis. The setters of handle options are host-only: what they set is
  *     baked into the launches captured after them.
  *   Not capturable (they hand a size or a flag back to the host, and
@@ -656,6 +657,63 @@ spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
                                const int* csrRowPtr, const int* csrColInd, int valueBytes,
                                const spmm_mat_descr_t descrC, void* cscVal, int* cscColPtr,
                                int* cscRowInd, int* perm);
+
+/* CSR-sampled dense-dense product (SDDMM, cusparseSDDMM's shape; no reference
+ * counterpart): for every position p of the m x k CSR pattern
+ *     outVal[p] = epi(dot(X[i(p), 0..n), Y[j(p), 0..n)))
+ * with i(p) the row that holds p and j(p) = csrColInd[p] - base; epi(d) = alpha * d
+ * when beta == 0 (outVal is then never read), else fma(beta, outVal[p], alpha * d),
+ * the epilogue of the CSR products. With X = grad_C and Y = B it is the gradient of
+ * A's values in C = A * B; with X = Y = H the edge logits <h_i, h_j> of a graph.
+ *   X is m x n and Y is k x n, row-major fp32, ldx, ldy >= n counted in floats; X and
+ *     Y may be the same buffer. n = 0 is valid: the dot is +0.
+ *   csrColInd and outVal hold nnz entries and share their index: position p is index
+ *     p of both as passed, and the pattern holds the positions csrRowPtr[0] - base ..
+ *     csrRowPtr[m] - base (csrRowPtr[0] may exceed the base, as in spmm_csr2csc: a
+ *     view into a larger matrix; entries outside the view are left alone). Duplicate
+ *     (row, col) entries and rows not sorted by column are ordinary input.
+ *   The association rule: the bits of outVal[p] depend on the two rows, n, alpha,
+ *     beta and the old outVal[p] alone, never on the grid or the worker count, on
+ *     p's place in the array, on the row's length, on ldx / ldy or the operands'
+ *     alignment, or on the entry point (device = host, bit for bit).
+ *       G(n) = min(64, max(1, pow2ceil(ceil(n / 4)))) chains make one dot. Chain l
+ *       owns the columns c with (c / 4) mod G == l and sums them in ascending c as
+ *       acc = fma(x[c], y[c], acc) in fp32, starting from +0 (a chain without a
+ *       column stays +0). The chains fold in the butterfly acc_l + acc_(l xor s) for
+ *       s = 1, 2, ..., G / 2, that is pairwise over adjacent chains, level by level.
+ *       On the device a chain is a lane (64 / G positions per wave instruction); a
+ *       base that is not 16-byte aligned or an ld with ld % 4 != 0 changes how a
+ *       lane's words are loaded (single dwords instead of dwordx4), not which lane
+ *       sums them: the policy of the fp16 CSR entries.
+ *   Checks, in order: negative m, n, k or nnz, another base, ldx < n or ldy < n, or
+ *     a NULL pointer with nnz > 0 (X and Y only when n > 0) are
+ *     SPMM_STATUS_INVALID_VALUE; m == 0 or nnz == 0 returns success at once. The host
+ *     form also refuses (before it writes anything) a decreasing row pointer,
+ *     csrRowPtr[0] below the base, csrRowPtr[m] - base above nnz and a column
+ *     outside [0, k).
+ * Host pointers, worker threads like the other host conversions. */
+spmm_status_t spmm_sddmm_csr_host_f32(int m, int n, int k, int nnz, float alpha,
+                                      const int* csrRowPtr, const int* csrColInd,
+                                      spmm_index_base_t base, const float* X, int ldx,
+                                      const float* Y, int ldy, float beta, float* outVal);
+
+/* spmm_sddmm_csr_host_f32 on the device: the same contract and the same bits
+ * (tests/test_gpu_sddmm.py), device pointers, one kernel on the handle's stream
+ * (csrc/sddmm_kernels.hip). Every wave takes an equal share of the
+ * positions, so degree skew costs nothing; a lane group keeps its row's X slice in
+ * registers along a CSR row and has several Y-row gathers in flight.
+ *   A NULL handle is SPMM_STATUS_NOT_INITIALIZED before the checks above. A column
+ *     outside [0, k) or a bad row pointer is the caller's fault, as in
+ *     spmm_csrmm_ex_f32: there is no device-side validation and no read-back (the
+ *     positions are only ever clamped to [0, nnz), the rows to [0, m)).
+ *   The call does not synchronise, takes nothing from the handle's buffers (a
+ *     repeat allocates nothing, and it disturbs no other entry's state) and may be
+ *     captured into a graph; a replay re-reads the pattern, X, Y and outVal at the
+ *     captured addresses. With kernel timing on, its one kernel is timed. */
+spmm_status_t spmm_sddmm_csr_f32(spmm_handle_t handle, int m, int n, int k, int nnz, float alpha,
+                                 const int* csrRowPtr, const int* csrColInd,
+                                 spmm_index_base_t base, const float* X, int ldx, const float* Y,
+                                 int ldy, float beta, float* outVal);
 
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's

@@ -186,6 +186,22 @@ spmm_status_t spmm_csrmm_ex_f16(spmm_handle_t handle, int m, int n, int k, int n
                     orderB, beta, C, ldc, orderC);
 }
 
+spmm_status_t spmm_sddmm_csr_f32(spmm_handle_t handle, int m, int n, int k, int nnz, float alpha,
+                                 const int* csrRowPtr, const int* csrColInd,
+                                 spmm_index_base_t base, const float* X, int ldx, const float* Y,
+                                 int ldy, float beta, float* outVal) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < n || ldy < n) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !csrColInd || !outVal || (n > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  return launch_sddmm(handle, m, n, nnz, csrRowPtr, csrColInd, (int)base, X, ldx, Y, ldy, alpha,
+                      beta, outVal);
+}
+
 spmm_status_t spmm_csr_hot_analysis(spmm_handle_t handle, int n, int k, int nnz,
                                     const int* csrColInd, spmm_index_base_t base,
                                     long long hotBytes, int* csrColIndHot) {

@@ -173,6 +173,11 @@ spmm_status_t launch_csrmm_rowmajor_f16(spmm_context* ctx, int m, int n, const i
 spmm_status_t launch_csr_hot_analysis(spmm_context* ctx, int k, long long nnz, const int* colind,
                                       int base, long long hot_rows, int* colind_out);
 size_t csrmm_carry_bytes(spmm_context* ctx, int m, int n);
+// spmm_sddmm_csr_f32 (sddmm_kernels.hip): one launch, no workspace; nnz bounds the
+// positions and sizes the grid
+spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* rowptr,
+                           const int* colind, int base, const float* X, int ldx, const float* Y,
+                           int ldy, float alpha, float beta, float* out);
 
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst);

@@ -288,6 +288,80 @@ spmm_status_t spmm_csr2csc(int m, int n, int nnz, const void* csrVal, const int*
 
 }  // extern "C"
 
+namespace {
+
+// The dot of the sampled product's rule (include/spmm_hip.h): chain l of
+// G sums the columns c with (c / 4) mod G == l in ascending c by fp32 FMA from +0, and
+// the chains fold pairwise over adjacent lanes, level by level (the butterfly
+// acc_l + acc_(l xor s), s = 1, 2, ..., G / 2).
+inline int sddmm_group_lanes(int n) {
+  const int chunks = (n + 3) / 4;
+  int g = 1;
+  while (g < chunks && g < 64) g <<= 1;
+  return g;
+}
+
+inline float sddmm_dot(const float* x, const float* y, int n, int G) {
+  float acc[64];
+  for (int l = 0; l < G; ++l) {
+    float a = 0.f;
+    for (int c0 = 4 * l; c0 < n; c0 += 4 * G)
+      for (int c = c0; c < std::min(c0 + 4, n); ++c) a = __builtin_fmaf(x[c], y[c], a);
+    acc[l] = a;
+  }
+  for (int w = G; w > 1; w >>= 1)
+    for (int l = 0; l < w / 2; ++l) acc[l] = acc[2 * l] + acc[2 * l + 1];
+  return acc[0];
+}
+
+}  // namespace
+
+extern "C" {
+
+// The sampled dense-dense product on the host: the written rule in executable form (the
+// device entry, spmm_sddmm_csr_f32, equals it bit for bit). Workers take equal shares of
+// the positions; an output depends on its own two rows alone, so the worker count
+// cannot change a bit.
+spmm_status_t spmm_sddmm_csr_host_f32(int m, int n, int k, int nnz, float alpha,
+                                      const int* csrRowPtr, const int* csrColInd,
+                                      spmm_index_base_t base, const float* X, int ldx,
+                                      const float* Y, int ldy, float beta, float* outVal) {
+  if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < n || ldy < n) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !csrColInd || !outVal || (n > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)csrRowPtr[0] - ba, p1 = (int64_t)csrRowPtr[m] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (csrRowPtr[r + 1] < csrRowPtr[r]) ok = false;
+  });
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p)
+      if (csrColInd[p] - ba < 0 || csrColInd[p] - ba >= k) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  const int G = sddmm_group_lanes(n);
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    if (lo >= hi) return;
+    // the row of the share's first position: the last row that starts at or before it
+    int r = (int)(std::upper_bound(csrRowPtr, csrRowPtr + m, (int)(p0 + lo + ba)) - csrRowPtr) - 1;
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p) {
+      while (p >= (int64_t)csrRowPtr[r + 1] - ba) ++r;
+      const float d = sddmm_dot(X + (int64_t)r * ldx, Y + (int64_t)(csrColInd[p] - ba) * ldy, n, G);
+      outVal[p] = beta == 0.f ? alpha * d : __builtin_fmaf(beta, outVal[p], alpha * d);
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+}  // extern "C"
+
 // ----------------------------------------------------------------------------
 // divide_matrix (divide.cu:52-127) with values.
 // ----------------------------------------------------------------------------

@@ -1,13 +1,20 @@
-"""torch.autograd on top of ops: the fp32 CSR product with a gradient for B.
+"""torch.autograd on top of ops: the fp32 CSR product with gradients for B and for A's
+values.
 
 ops.py stays "torch only owns memory"; this module is the one place where the
-engine meets torch's autograd. Both directions run ops.csrmm (the merge-path
-kernel): the forward on A, the backward on A^T, which CsrMatrix.t() builds once
-per matrix with ops.csr2csc (the device transpose) and keeps.
+engine meets torch's autograd. The forward and grad_B run ops.csrmm (the merge-path
+kernel), the forward on A, grad_B on A^T, which CsrMatrix.t() builds once per matrix
+with ops.csr2csc (the device transpose) and keeps together with the permutation that
+carries values over; grad_val runs ops.sddmm (the sampled dense-dense product) on A's
+own pattern.
 
     A = CsrMatrix(rowptr, colind, val, m, k)      # device tensors, base 0
     H1 = spmm(A, H)                               # H requires grad
     H1.sum().backward()                           # H.grad = A^T * dH1
+
+    w = edge_weights(...)                         # nnz floats, requires grad
+    H1 = spmm(A, H, val=w)                        # w replaces A.val for this product
+    H1.sum().backward()                           # w.grad[p] = <dH1[row(p)], H[col(p)]>
 """
 from __future__ import annotations
 
@@ -32,27 +39,44 @@ class CsrMatrix:
         self.rowptr, self.colind, self.val = rowptr, colind, val
         self.m, self.k = m, k
         self._t: CsrMatrix | None = None
+        self._perm: torch.Tensor | None = None  # t().val == val[_perm] (t_perm)
 
     def t(self, handle: ops.Handle | None = None) -> "CsrMatrix":
         """The k x m transpose: ops.csr2csc on the first call, the same object on every
         later one; its own .t() is this matrix. Its rows are sorted by column, entries
         of equal (row, col) in this matrix's order."""
         if self._t is None:
-            cp, ri, v = ops.csr2csc(self.rowptr, self.colind, self.val.detach(), m=self.m,
-                                    n=self.k, nnz=self.colind.numel(), handle=handle)
+            cp, ri, v, perm = ops.csr2csc(self.rowptr, self.colind, self.val.detach(), m=self.m,
+                                          n=self.k, nnz=self.colind.numel(), return_perm=True,
+                                          handle=handle)
             At = CsrMatrix(cp, ri, v, self.k, self.m)
             At._t = self
             self._t = At
+            self._perm = perm
         return self._t
 
+    def t_perm(self, handle: ops.Handle | None = None) -> torch.Tensor:
+        """int32[nnz] with t().val == val[t_perm()]: the transpose's own permutation
+        (ops.csr2csc's perm), kept with it. On a matrix that is itself a cached transpose
+        it is the inverse of the other side's, derived once by a scatter of arange (a
+        permutation has no repeated target, so the scatter is deterministic)."""
+        At = self.t(handle)
+        if self._perm is None:
+            p = At._perm
+            inv = torch.empty_like(p)
+            inv[p.long()] = torch.arange(p.numel(), dtype=torch.int32, device=p.device)
+            self._perm = inv
+        return self._perm
 
-def _product(A: CsrMatrix, B: torch.Tensor) -> torch.Tensor:
+
+def _product(A: CsrMatrix, B: torch.Tensor, val: torch.Tensor | None = None) -> torch.Tensor:
     if B.dim() != 2 or B.shape[0] != A.k:
         raise ValueError(f"spmm: B must be ({A.k}, K), got {tuple(B.shape)}")
     B = B.contiguous()
     K = B.shape[1]
     C = torch.empty((A.m, K), dtype=torch.float32, device=B.device)
-    return ops.csrmm(A.rowptr, A.colind, A.val.detach(), B, m=A.m, n=K, k=A.k, ldb=K, C=C, ldc=K)
+    v = A.val.detach() if val is None else val
+    return ops.csrmm(A.rowptr, A.colind, v, B, m=A.m, n=K, k=A.k, ldb=K, C=C, ldc=K)
 
 
 class _Spmm(torch.autograd.Function):
@@ -67,21 +91,61 @@ class _Spmm(torch.autograd.Function):
         return grad_B, None
 
 
-def spmm(A: CsrMatrix, B: torch.Tensor) -> torch.Tensor:
+class _SpmmVal(torch.autograd.Function):
+    """The product on A's pattern with the values of a tensor of its own."""
+
+    @staticmethod
+    def forward(ctx, B: torch.Tensor, val: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        B, val = B.detach().contiguous(), val.detach().contiguous()
+        ctx.save_for_backward(B, val)
+        return _product(A, B, val)
+
+    @staticmethod
+    def backward(ctx, grad_C: torch.Tensor):
+        A = ctx.A
+        B, val = ctx.saved_tensors
+        grad_C = grad_C.contiguous()
+        grad_B = grad_val = None
+        if ctx.needs_input_grad[0]:
+            vt = torch.index_select(val, 0, A.t_perm())
+            grad_B = _product(A.t(), grad_C, vt)
+        if ctx.needs_input_grad[1]:
+            grad_val = ops.sddmm(A.rowptr, A.colind, grad_C, B, m=A.m, n=B.shape[1], k=A.k)
+        return grad_B, grad_val, None
+
+
+def spmm(A: CsrMatrix, B: torch.Tensor, val: torch.Tensor | None = None) -> torch.Tensor:
     """C = A * B (fp32, row-major B[k, K] and C[m, K]): exactly ops.csrmm in the forward,
     and grad_B = ops.csrmm on A.t() applied to grad_C in the backward (the bits of the
-    piece rule on A^T). A.val gets no gradient: that is a sampled dense-dense product,
-    another kernel, which this library does not have; a val that requires grad is
-    refused here, not silently treated as a constant."""
+    piece rule on A^T).
+
+    val=None: the values are A.val, a constant: it gets no gradient, and an A.val that
+    requires grad is refused here, not silently treated as a constant; pass it as val.
+
+    val: a float32 device tensor of nnz entries that replaces A.val for this product and
+    may require grad (learned or computed edge weights on a fixed pattern). The forward
+    is ops.csrmm on (A.rowptr, A.colind, val); the backward gives
+    grad_val = ops.sddmm(A.rowptr, A.colind, grad_C, B), the sampled dense-dense product
+    grad_val[p] = <grad_C[row(p), :], B[col(p), :]>, and grad_B = ops.csrmm on A.t()'s
+    pattern with the values val[A.t_perm()]. Each gradient is computed only when it is
+    needed: the transpose is not built for grad_val alone."""
     if not isinstance(A, CsrMatrix):
         raise TypeError("spmm: A must be a CsrMatrix")
-    if A.val.requires_grad:
-        raise ValueError("spmm: A.val requires grad, but only B gets a gradient (the gradient "
-                         "of the values is a sampled dense-dense product, not provided); "
-                         "detach A.val")
+    if val is None and A.val.requires_grad:
+        raise ValueError("spmm: A.val requires grad, but only B gets a gradient on this "
+                         "path; pass the values as spmm(A, B, val=...) to get theirs "
+                         "(ops.sddmm), or detach A.val")
     if not isinstance(B, torch.Tensor) or B.dtype != torch.float32 or not B.is_cuda:
         raise TypeError("spmm: B must be a float32 tensor on a HIP device")
-    return _Spmm.apply(B, A)
+    if val is None:
+        return _Spmm.apply(B, A)
+    if not isinstance(val, torch.Tensor) or val.dtype != torch.float32 or not val.is_cuda:
+        raise TypeError("spmm: val must be a float32 tensor on a HIP device")
+    if val.dim() != 1 or val.numel() != A.colind.numel():
+        raise ValueError(f"spmm: val must hold the pattern's {A.colind.numel()} values, got "
+                         f"{tuple(val.shape)}")
+    return _SpmmVal.apply(B, val, A)
 
 
 __all__ = ["CsrMatrix", "spmm"]

@@ -11,6 +11,7 @@ through the C ABI. The functions mirror the reference's operator interfaces:
   bsrmm_f16(...)      fp16 A/B, fp32 accumulate (config 5)
   csrmm_f16(...) / gespmm_csrmm_f16(...)
                       csrmm / gespmm_csrmm with fp16 A/B, fp32 accumulate and C
+  sddmm(...)          cusparseSDDMM's shape on a CSR pattern: out[p] = <X[row(p)], Y[col(p)]>
 """
 from __future__ import annotations
 
@@ -203,6 +204,46 @@ def gespmm_csrmm_f16(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tens
                                       _ptr(C), c_void_p(torch.cuda.current_stream().cuda_stream)),
           "spmm_gespmm_csrmm_f16")
     return C
+
+
+def sddmm(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *,
+          m: int | None = None, n: int | None = None, k: int, ldx: int | None = None,
+          ldy: int | None = None, out: torch.Tensor | None = None, alpha: float = 1.0,
+          beta: float = 0.0, base: int = 0, handle: Handle | None = None) -> torch.Tensor:
+    """CSR-sampled dense-dense product (spmm_sddmm_csr_f32): for every position p of the
+    m x k pattern, out[p] = alpha * <X[row(p), :n], Y[colind[p] - base, :n]> (+ beta *
+    out[p]; beta == 0 never reads out). X (m x n) and Y (k x n) are row-major fp32 with
+    leading dimensions ldx, ldy (default: n; n defaults to a 2-D X's column count) and
+    may be the same tensor. out has colind's length and index (default: a new tensor;
+    with a rowptr that is a view, rowptr[0] > base, only the view's positions are
+    written). One kernel on the handle's stream: no synchronisation, no workspace,
+    capturable. The bits follow the rule of include/spmm_hip.h and equal prep.sddmm's."""
+    for t, d, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                     (X, torch.float32, "X"), (Y, torch.float32, "Y")):
+        _need(t, d, nm)
+    m = rowptr.numel() - 1 if m is None else m
+    if n is None:
+        if X.dim() != 2:
+            raise ValueError("sddmm: n is needed when X is not a 2-D tensor")
+        n = X.shape[1]
+    ldx = n if ldx is None else ldx
+    ldy = n if ldy is None else ldy
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"sddmm: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    for t, rows, ld, nm in ((X, m, ldx, "X"), (Y, k, ldy, "Y")):
+        if ld < n or (rows > 0 and t.numel() < (rows - 1) * ld + n):
+            raise ValueError(f"sddmm: {nm} holds {t.numel()} floats, {rows} rows of {n} with "
+                             f"leading dimension {ld} need {max(rows - 1, 0) * ld + n}")
+    if out is None:
+        out = torch.empty(colind.numel(), dtype=torch.float32, device=colind.device)
+    _need(out, torch.float32, "out")
+    if out.numel() < colind.numel():
+        raise ValueError("sddmm: out is shorter than colind")
+    h = handle or default_handle()
+    check(lib().spmm_sddmm_csr_f32(h.raw, m, n, k, colind.numel(), alpha, _ptr(rowptr),
+                                   _ptr(colind), base, _ptr(X), ldx, _ptr(Y), ldy, beta,
+                                   _ptr(out)), "spmm_sddmm_csr_f32")
+    return out
 
 
 def csr_hot_analysis(colind: torch.Tensor, *, n: int, k: int, base: int = 0,
@@ -750,5 +791,5 @@ class MultiGPU:
 
 
 __all__ = ["coo2csr", "MultiGPU", "csr2bsr", "csr2csc", "bsr2csr", "Handle", "hybrid_csrmm", "default_handle", "gespmm_csrmm", "csrmm", "bsrmm", "bsrmm_f16",
-           "csrmm_f16", "gespmm_csrmm_f16",
+           "csrmm_f16", "gespmm_csrmm_f16", "sddmm",
            "SpmmError", "ORDER_ROW", "ORDER_COL"]

@@ -1,7 +1,7 @@
 """Host-side preprocessing and data feeders (numpy in, numpy out).
 
 Thin wrappers over the C ABI of libspmm_hip.so:
-  csr2bsr / bsr2csr / csr2csc / calculate_nnzb / partition_rows   (include/spmm_hip.h)
+  csr2bsr / bsr2csr / csr2csc / sddmm / calculate_nnzb / partition_rows   (include/spmm_hip.h)
   rng_seed / random_array / random_csr / random_bsr /
   load_csr / dump_csr / load_graph / save_csr_bin / load_csr_bin / load_csr_cached /
   powerlaw_csr / community_csr                                  (include/spmm_host.h)
@@ -110,6 +110,38 @@ def csr2csc(m: int, n: int, rowptr, colind, val=None, *, base: int = 0,
         out += (cval,)
     if return_perm:
         out += (perm,)
+    return out
+
+
+def sddmm(m: int, n: int, k: int, rowptr, colind, X, Y, *, ldx: int | None = None,
+          ldy: int | None = None, out=None, alpha: float = 1.0, beta: float = 0.0,
+          base: int = 0) -> np.ndarray:
+    """spmm_sddmm_csr_host_f32: out[p] = alpha * <X[row(p), :n], Y[colind[p] - base, :n]>
+    (+ beta * out[p]) for every position p of the m x k CSR pattern, by the association
+    rule of include/spmm_hip.h (the bits of ops.sddmm). X (m x n) and Y (k x n): float32,
+    row-major with leading dimensions ldx, ldy (default n), 2-D or flat. out: float32 of
+    colind's length and index (default zeros; returned). rowptr[0] may exceed `base`."""
+    rowptr, colind = _i32(rowptr), _i32(colind)
+    if rowptr.size != m + 1:
+        raise ValueError(f"sddmm: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    ldx = n if ldx is None else ldx
+    ldy = n if ldy is None else ldy
+    ops_ = []
+    for a, rows, ld, nm in ((X, m, ldx, "X"), (Y, k, ldy, "Y")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous:
+            raise TypeError(f"sddmm: {nm} must be a C-contiguous float32 array")
+        if ld < n or (rows > 0 and a.size < (rows - 1) * ld + n):
+            raise ValueError(f"sddmm: {nm} holds {a.size} floats, {rows} rows of {n} with "
+                             f"leading dimension {ld} need {max(rows - 1, 0) * ld + n}")
+        ops_.append(a)
+    if out is None:
+        out = np.zeros(colind.size, dtype=np.float32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or \
+            not out.flags.c_contiguous or out.size < colind.size:
+        raise TypeError("sddmm: out must be a C-contiguous float32 array of colind's length")
+    check(lib().spmm_sddmm_csr_host_f32(m, n, k, colind.size, alpha, _p(rowptr), _p(colind), base,
+                                        _p(ops_[0]), ldx, _p(ops_[1]), ldy, beta, _p(out)),
+          "spmm_sddmm_csr_host_f32")
     return out
 
 
