@@ -803,7 +803,11 @@ spmm_status_t spmm_set_hybrid_options(spmm_handle_t handle, int flags);
  * block rows), A_csr the remainder. When nnzb > 0, B must hold
  * ceil(k/bs)*bs rows and C ceil(m/bs)*bs rows (padded, as the reference's
  * drivers allocate them, run_bsrmm.cu:86-94). The BSR part runs on MFMA
- * (writing C with beta), then the CSR part accumulates (beta = 1). */
+ * (writing C with beta), then the CSR part accumulates (beta = 1): the result
+ * is the sum of two rounded products, fma(1, fma(beta, C, alpha * S_bsr),
+ * alpha * S_csr), fused launch or not. Where the two parts cancel exactly it
+ * is +0; one sum over both parts would give alpha * (+0), a -0 under a
+ * negative alpha (tests/test_gpu_edge_values.py::test_hybrid_csrmm_f32). */
 spmm_status_t spmm_hybrid_csrmm_f32(spmm_handle_t handle, int m, int n, int k, float alpha,
                                     const int* csrRowPtr, const int* csrColInd,
                                     const float* csrVal, int csrNnz, int blockDim,
