@@ -28,6 +28,10 @@
 #include <utility>
 
 #include "context.hpp"
+#ifdef SPMM_DISPATCH_TRACE
+#include "dispatch_trace.hpp"  // first: dispatch.hpp's launch status goes through it too
+#endif
+#include "dispatch.hpp"
 
 namespace {
 
@@ -3951,37 +3955,13 @@ constexpr int kBsr16F16Cm = 4725;
 //  bs 16 fp32: the column-masked block kernel (products stand-in K = 512
 //  16.6 ms against 18.5 for the full-panel kernel).
 
-#ifdef SPMM_TUNING
+// TUNING builds only (tuning_env_int: a release build has the defaults compiled in).
 // SPMM_SMALL_GRP=0: bs 2 / 4 / 8 on bsr_small_kernel instead of the grouped MFMA
 // stream, for A/B timing
-bool small_grp_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SPMM_SMALL_GRP");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-int variant_override() {
-  static const int var = [] {
-    const char* e = getenv("SPMM_BSR_VARIANT");
-    return e ? atoi(e) : -1;
-  }();
-  return var;
-}
+bool small_grp_enabled() { return tuning_env_int("SPMM_SMALL_GRP", 1) != 0; }
+int variant_override() { return tuning_env_int("SPMM_BSR_VARIANT", -1); }
 // SPMM_BSR_ORDER=1 / 2 / 3 (below): scheduling A/B of the column streams
-int order_override() {
-  static const int force = [] {
-    const char* e = getenv("SPMM_BSR_ORDER");
-    return e ? atoi(e) : 0;
-  }();
-  return force;
-}
-#else
-constexpr bool small_grp_enabled() { return true; }
-constexpr int variant_override() { return -1; }
-constexpr int order_override() { return 0; }
-#endif
-#define SPMM_COMMA ,
+int order_override() { return tuning_env_int("SPMM_BSR_ORDER", 0); }
 
 // Block-row order for the column-stream kernels: longest first when the grid
 // is at most kLptRounds waves per resident slot deep (a few long rows would
@@ -4042,28 +4022,471 @@ spmm_status_t block_row_order(spmm_context* ctx, int mb, int ntiles, const int* 
   return SPMM_STATUS_SUCCESS;
 }
 
-#define SPMM_BSR_DISPATCH(KERNEL, TA, GRID, BLOCK, STREAM, ROWD, BR, CR, ...)                 \
-  do {                                                                                    \
-    if (ROWD) {                                                                           \
-      if (BR) {                                                                           \
-        if (CR) hipLaunchKernelGGL((KERNEL<true, true, true TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);   \
-        else hipLaunchKernelGGL((KERNEL<true, true, false TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);     \
-      } else {                                                                            \
-        if (CR) hipLaunchKernelGGL((KERNEL<true, false, true TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL<true, false, false TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);    \
-      }                                                                                   \
-    } else {                                                                              \
-      if (BR) {                                                                           \
-        if (CR) hipLaunchKernelGGL((KERNEL<false, true, true TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL<false, true, false TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);    \
-      } else {                                                                            \
-        if (CR) hipLaunchKernelGGL((KERNEL<false, false, true TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<false, false, false TA>), GRID, BLOCK, 0, STREAM, __VA_ARGS__);   \
-      }                                                                                   \
-    }                                                                                     \
-  } while (0)
+// ---------------------------------------------------------------------------
+// Dispatch. launch_bsrmm_f32 / launch_bsrmm_f16 are routers: a chain of the predicates
+// below, each followed by one call of a path function. Run-time choices reach template
+// arguments through with_bools / with_int (dispatch.hpp); which instantiation, grid and
+// arguments an argument tuple reaches is pinned by tests/test_dispatch_trace.py.
+// ---------------------------------------------------------------------------
+
+// One product's arguments, as the fp32 (T = float) and fp16 (T = _Float16) entries take them.
+template <typename T>
+struct BsrArgs {
+  spmm_context* ctx;
+  int mb, kb, n, nnzb, bs;
+  float alpha;
+  const int *rowptr, *colind;
+  const T *val, *B;
+  int ldb;
+  float beta;
+  float* C;
+  int ldc;
+  bool rowd, brow, crow;  // ROW blocks, row-major B, row-major C
+  const unsigned* masks;  // the analysis' column masks, or null
+};
 
 bool aligned(const void* p, int bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+
+// The copy kernels read A and row-major B as 16-byte pieces: vec elements (4 floats, 8
+// halves) divide n and ldb, and val and B are 16-byte aligned.
+bool b_rows_copyable(int n, int ldb, const void* val, const void* B, int vec) {
+  return n >= vec && n % vec == 0 && ldb % vec == 0 && aligned(val, 16) && aligned(B, 16);
+}
+// The column streams store row-major C as 16-B row pieces (and the segment fix-up too): C
+// and ldc must keep them aligned, else the fragment kernel's scalar stores serve.
+bool c_rows_storable(bool crow, const float* C, int ldc) {
+  return !crow || (aligned(C, 16) && ldc % 4 == 0);
+}
+// The register-fragment kernels load A fragments, and column-major B ones, as 16-byte vectors.
+bool fragments_loadable(const void* val, bool brow, const void* B, int ldb, int vec) {
+  return aligned(val, 16) && (brow || (aligned(B, 16) && ldb % vec == 0));
+}
+// 32-row panels of B addressable in 31 bits (the streams' 32-bit B-row offsets, O32)
+bool panels_in_31_bits(int ldb) { return (size_t)ldb * 128 < (1u << 31); }
+
+// The analysed bs 32 column stream: COLUMN blocks with their column masks.
+bool bs32_analysed(const BsrArgs<float>& a, bool dense_blocks) {
+  return a.masks && a.bs == 32 && !a.rowd && !dense_blocks &&
+         c_rows_storable(a.crow, a.C, a.ldc);
+}
+// bs 32 on the copy kernels: the column stream, or the LDS kernel for blocks known dense
+// (which stores C from registers: no alignment asked of it).
+bool bs32_copy_kernels(const BsrArgs<float>& a, bool dense_blocks) {
+  return a.bs == 32 && (a.rowd || bs32_analysed(a, dense_blocks)) && a.brow &&
+         b_rows_copyable(a.n, a.ldb, a.val, a.B, 4) &&
+         (dense_blocks || c_rows_storable(a.crow, a.C, a.ldc));
+}
+// bs 64: the bs 32 column stream on the four 32 x 32 sub-blocks of each block.
+bool bs64_sub_stream_ok(const BsrArgs<float>& a, bool dense_sem) {
+  return a.bs == 64 && a.rowd && a.brow && b_rows_copyable(a.n, a.ldb, a.val, a.B, 4) &&
+         c_rows_storable(a.crow, a.C, a.ldc) && !dense_sem;
+}
+// bs 16 fp32: the column-masked block kernel.
+bool bs16_column_masked_ok(const BsrArgs<float>& a, bool dense_sem) {
+  return a.bs == 16 && a.rowd && a.brow && b_rows_copyable(a.n, a.ldb, a.val, a.B, 4) &&
+         !dense_sem;
+}
+bool small_bs(int bs) { return bs == 2 || bs == 4 || bs == 8; }
+// bs 2 / 4 / 8 on the grouped MFMA stream: 8-byte B gathers, 16-byte C row pieces, its
+// 32-bit offsets, and from 2^20 blocks only (its fixed cost, the probe and the order,
+// about 40 us, made the reference sweep's small cells up to 2x slower;
+// SPMM_BSR_SMALL_GROUPED forces it).
+bool small_grouped_ok(const BsrArgs<float>& a, bool dense_sem) {
+  return small_bs(a.bs) && a.brow && !dense_sem && a.nnzb > 0 && a.n >= 4 && a.n % 4 == 0 &&
+         a.ldb % 2 == 0 && aligned(a.B, 8) && aligned(a.val, 16) &&
+         c_rows_storable(a.crow, a.C, a.ldc) && a.kb < (1 << 26) &&
+         (size_t)a.ldb * a.bs * 4 < (1u << 31) &&
+         (size_t)(32 / a.bs) * a.kb * a.bs * a.bs * 4 < (1u << 31) &&
+         (a.nnzb >= (1 << 20) || (a.ctx->bsr_flags & SPMM_BSR_SMALL_GROUPED)) &&
+         small_grp_enabled();
+}
+// bs 2 / 4 / 8 on the lane-group VALU kernel (row-major B).
+bool small_valu_ok(const BsrArgs<float>& a, bool dense_sem) {
+  return small_bs(a.bs) && a.brow && !dense_sem;
+}
+// The analysed bs 16 fp16 column stream: COLUMN blocks with their column masks, n >= 128.
+bool bs16_f16_analysed(const BsrArgs<_Float16>& a, bool dense_sem) {
+  return a.masks && a.bs == 16 && !a.rowd && a.n >= 128 && !dense_sem;
+}
+// bs 16 fp16 on the copy kernels (column stream or column-masked).
+bool bs16_f16_copy_kernels(const BsrArgs<_Float16>& a, bool dense_sem) {
+  return a.bs == 16 && (a.rowd || bs16_f16_analysed(a, dense_sem)) && a.brow &&
+         b_rows_copyable(a.n, a.ldb, a.val, a.B, 8) && !dense_sem;
+}
+
+// The panel probe's sums (ctx->scratch) over nblocks 32 x 32 blocks (sub: sub-blocks of
+// bs 64 blocks), zeroed and filled in stream order: the stream and the panel kernel both
+// go out, the sums choose on the device (no host round trip, graph-capturable).
+spmm_status_t panel_probe(spmm_context* ctx, long long nblocks, int sub, const float* val,
+                          unsigned long long** pstat) {
+  if (spmm_status_t st = spmm::ensure_scratch(ctx, 2 * sizeof(unsigned long long))) return st;
+  *pstat = static_cast<unsigned long long*>(ctx->scratch);
+  if (hipError_t e = hipMemsetAsync(*pstat, 0, 2 * sizeof(**pstat), ctx->stream))
+    return spmm::from_hip(e);
+  const int ns = (int)std::min<long long>(nblocks, kPanelSamples);
+  hipLaunchKernelGGL(panel_probe_kernel, dim3((ns + 4 * kPanelPerWave - 1) / (4 * kPanelPerWave)),
+                     dim3(256), 0, ctx->stream, nblocks, ns, sub, val, *pstat);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// The panel stream (same bits as the column stream) over mbx rows of 32 x 32 blocks.
+template <bool SUB>
+void launch_panel(const BsrArgs<float>& a, dim3 grid, int mbx, const int* ord,
+                  const unsigned long long* pstat) {
+  spmm::with_bools(
+      [&](auto cr, auto c64) {
+        constexpr bool CR = decltype(cr)::value, C64 = decltype(c64)::value;
+        hipLaunchKernelGGL(
+            (bsr32_f32_panel_kernel<CR, C64, C64 ? SPMM_PANEL_D64 : SPMM_PANEL_D128, SUB>), grid,
+            dim3(64), 0, a.ctx->stream, mbx, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb, a.alpha,
+            a.beta, a.C, a.ldc, ord, pstat);
+      },
+      a.crow, a.n <= 64);
+}
+
+// bs 32, blocks known dense: the full-panel LDS kernel (kBsr32Dense). split: split-bf16
+// (opt-in, SPMM_HYBRID_SPLIT_BF16): wave-pair split-K for row-major C (products hybrid
+// 1.86-1.87 vs 1.89 ms fused, reddit 0.80 vs 0.83, profiles/r01_hybrid_split.jsonl), one k
+// range per wave for column-major C.
+spmm_status_t bs32_dense_lds(const BsrArgs<float>& a, bool split) {
+  const dim3 grid(a.mb, (a.n + 127) / 128);
+  spmm::with_bools(
+      [&](auto cr, auto sp) {
+        constexpr bool CR = decltype(cr)::value, SP = decltype(sp)::value;
+        hipLaunchKernelGGL((bsr32_f32_lds_kernel<CR, 2, 32, false, 24, SP, SP && CR>), grid,
+                           dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
+                           a.ldb, a.alpha, a.beta, a.C, a.ldc, nullptr, nullptr, nullptr, 0,
+                           nullptr);
+      },
+      a.crow, split);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 32 column stream, variant lv (kBsr32Cs, or a TUNING override; kBsr32CsWideLdb when
+// the panels need 64-bit offsets), or its analysed form (msk). Segments of outlier rows
+// (row-major C, shallow grids) or the longest-first order (shallow grids), else the
+// XCD-chunked order.
+spmm_status_t bs32_column_stream(const BsrArgs<float>& a, bool msk, int lv) {
+  spmm_context* ctx = a.ctx;
+  const unsigned ntiles = (a.n + 127) / 128;
+  const bool narrow = panels_in_31_bits(a.ldb);
+  const int* ord = nullptr;
+  const int4 *sg = nullptr, *spl = nullptr;
+  float* pt = nullptr;
+  int nsg = 0, nspl = 0;
+  if (a.crow)
+    if (spmm_status_t st =
+            cs2_segments(ctx, a.mb, a.nnzb, ntiles, a.rowptr, &sg, &spl, &pt, &nsg, &nspl))
+      return st;
+  if (!sg)
+    if (spmm_status_t st = block_row_order(ctx, a.mb, ntiles, a.rowptr, &ord)) return st;
+  const dim3 g2(sg ? nsg : a.mb, ntiles);
+  // n <= 64: the 64-column tile (C64; grid.y is 1 either way, so the segments' partial
+  // layout is the same)
+  const bool c64 = a.n <= 64;
+  // the panel stream when the probe finds the blocks dense
+  unsigned long long* pstat = nullptr;
+  if (!msk && !sg && lv == kBsr32Cs && a.nnzb >= kPanelMinBlocks)
+    if (spmm_status_t st = panel_probe(ctx, a.nnzb, 0, a.val, &pstat)) return st;
+  // (4, 8 or 10 items in flight: 2.11-2.15 / 2.11-2.12 / 2.43 ms against 2.11 at 6 on
+  // the products stand-in, profiles/r03_analysed_sweep.txt)
+  if (msk) {
+    spmm::with_bools(
+        [&](auto cr, auto o32, auto c64_) {
+          constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
+                         C64 = decltype(c64_)::value;
+          hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, true, false, C64>),
+                             g2, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val,
+                             a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt, a.masks);
+        },
+        a.crow, narrow, c64);
+  } else {
+    // 32-bit offsets O32 and nt A copies ANT, by variant
+    auto stream = [&](auto o32, auto ant) {
+      spmm::with_bools(
+          [&](auto cr, auto c64_) {
+            constexpr bool CR = decltype(cr)::value, C64 = decltype(c64_)::value;
+            hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, decltype(o32)::value, true,
+                                                     decltype(ant)::value, false, false, C64>),
+                               g2, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind,
+                               a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt,
+                               a.masks, pstat);
+          },
+          a.crow, c64);
+    };
+    if (lv == kBsr32Cs) stream(std::true_type{}, std::true_type{});
+    else if (lv == kBsr32CsNoNt) stream(std::true_type{}, std::false_type{});
+    else stream(std::false_type{}, std::true_type{});  // kBsr32CsWideLdb
+  }
+  if (pstat) launch_panel<false>(a, g2, a.mb, ord, pstat);
+  if (spl)
+    hipLaunchKernelGGL(seg_fixup_kernel, dim3(nspl, ntiles), dim3(256), 0, ctx->stream, a.n, spl,
+                       pt, a.alpha, a.beta, a.C, a.ldc);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 32 on the copy kernels: which of the two, and the stream's variant.
+spmm_status_t bs32_copy(const BsrArgs<float>& a, bool dense_blocks, bool hybrid_part) {
+  if (dense_blocks)  // (a tuning override never replaces the dense-block kernel)
+    return bs32_dense_lds(a, hybrid_part && (a.ctx->hybrid_flags & SPMM_HYBRID_SPLIT_BF16));
+  const int var = variant_override();
+  int lv = var == kBsr32CsNoNt || var == kBsr32CsWideLdb ? var : kBsr32Cs;
+  if (!panels_in_31_bits(a.ldb)) lv = kBsr32CsWideLdb;
+  return bs32_column_stream(a, bs32_analysed(a, dense_blocks), lv);
+}
+
+// bs 64: the bs 32 column stream on the four 32 x 32 sub-blocks of each block (SUB), one
+// wave per 32-row half of a block row and 128 columns.
+spmm_status_t bs64_sub_stream(const BsrArgs<float>& a) {
+  spmm_context* ctx = a.ctx;
+  const int mb2 = 2 * a.mb;
+  const dim3 g2(mb2, (a.n + 127) / 128);
+  const bool narrow = panels_in_31_bits(a.ldb);
+  const int* ord = nullptr;
+  if (spmm_status_t st = block_row_order(ctx, mb2, g2.y, a.rowptr, &ord, 12, nullptr, 0, 1))
+    return st;
+  // the panel stream over the sub-blocks when the probe finds them dense (same bits)
+  unsigned long long* pstat = nullptr;
+  if (narrow && 4LL * a.nnzb >= kPanelMinBlocks)
+    if (spmm_status_t st = panel_probe(ctx, 4LL * a.nnzb, 1, a.val, &pstat)) return st;
+  spmm::with_bools(
+      [&](auto cr, auto o32, auto c64) {  // c64: the 64-column tile
+        constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
+                       C64 = decltype(c64)::value;
+        hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, false, true, C64>),
+                           g2, dim3(64), 0, ctx->stream, mb2, a.n, a.rowptr, a.colind, a.val, a.B,
+                           a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, nullptr, nullptr, nullptr,
+                           pstat);
+      },
+      a.crow, narrow, a.n <= 64);
+  if (pstat) launch_panel<true>(a, g2, mb2, ord, pstat);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// The register-fragment fallback (bs 32 fp32, bs 16 fp32 / fp16): a wave owns 32 (bs 32)
+// or 64 (bs 16) output columns, 1 / 2 / 4 waves per workgroup by n.
+template <typename T>
+spmm_status_t fragment_fallback(const BsrArgs<T>& a) {
+  const int cols = a.bs == 32 ? 32 : 64;
+  const int waves = a.n <= cols ? 1 : (a.n <= 2 * cols ? 2 : 4);
+  const dim3 grid(a.mb, (a.n + cols * waves - 1) / (cols * waves)), block(64 * waves);
+  spmm::with_bools(
+      [&](auto rd, auto br, auto cr) {
+        constexpr bool RD = decltype(rd)::value, BR = decltype(br)::value,
+                       CR = decltype(cr)::value;
+        if constexpr (std::is_same_v<T, _Float16>)
+          hipLaunchKernelGGL((bsr16_f16_mfma_kernel<RD, BR, CR, kBsr16F16Default>), grid, block, 0,
+                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                             a.alpha, a.beta, a.C, a.ldc);
+        else if (a.bs == 32)
+          hipLaunchKernelGGL((bsr32_f32_mfma_kernel<RD, BR, CR, kBsr32Default>), grid, block, 0,
+                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                             a.alpha, a.beta, a.C, a.ldc);
+        else
+          hipLaunchKernelGGL((bsr16_f32_mfma_kernel<RD, BR, CR, kBsr16Default>), grid, block, 0,
+                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                             a.alpha, a.beta, a.C, a.ldc);
+      },
+      a.rowd, a.brow, a.crow);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 16 fp32, column-masked. Output columns per workgroup: 256, or the narrower tile a
+// small n fills (at n = 64 a 256-column tile left 3 of its 4 waves idle: reference sweep,
+// profiles/r05_sweep/).
+spmm_status_t bs16_column_masked(const BsrArgs<float>& a) {
+  const int cols = a.n <= 64 ? 64 : (a.n <= 128 ? 128 : 256);
+  const dim3 grid(a.mb, (a.n + cols - 1) / cols);
+  spmm::with_int<64, 128, 256>(cols, [&](auto co) {
+    spmm::with_bools(
+        [&](auto cr) {
+          hipLaunchKernelGGL(
+              (bsr16_cm_kernel<float, decltype(cr)::value, 2, 5, 1, decltype(co)::value>), grid,
+              dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+              a.alpha, a.beta, a.C, a.ldc);
+        },
+        a.crow);
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bsr_small_kernel (bs 2 / 4 / 8, the lane-group VALU kernel) over a.mb block rows: 2
+// floats per lane (v2) or 1; tail: xm, or the grouped stream's (xm, dirty tiles, tiles).
+template <typename... Tail>
+void launch_small(const BsrArgs<float>& a, bool v2, Tail... tail) {
+  const dim3 grid((a.mb + 3) / 4, (a.n + (v2 ? 127 : 63)) / (v2 ? 128 : 64));
+  spmm::with_int<2, 4, 8>(a.bs, [&](auto bs) {
+    spmm::with_bools(
+        [&](auto v2_, auto rd, auto cr) {
+          hipLaunchKernelGGL((bsr_small_kernel<decltype(bs)::value, decltype(v2_)::value ? 2 : 1,
+                                               decltype(rd)::value, decltype(cr)::value>),
+                             grid, dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind,
+                             a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, tail...);
+        },
+        v2, a.rowd, a.crow);
+  });
+}
+
+// bs 2 / 4 / 8, the grouped MFMA stream: 32 / bs block rows per wave share each B row of
+// their union. The choice per matrix first (small_grp_probe_kernel), then the stream, then
+// bsr_small_kernel on the tiles it flagged.
+spmm_status_t small_grouped(const BsrArgs<float>& a) {
+  spmm_context* ctx = a.ctx;
+  const int bs = a.bs;
+  const int ngroups = (a.mb + 32 / bs - 1) / (32 / bs);
+  const dim3 grid(ngroups, (a.n + 127) / 128);
+  if (spmm_status_t st =
+          spmm::ensure_scratch(ctx, (size_t)ngroups * grid.y * sizeof(int) + 256))
+    return st;
+  // the probe's integer sums
+  unsigned long long* stat = static_cast<unsigned long long*>(ctx->scratch);
+  int* dirty = reinterpret_cast<int*>(static_cast<char*>(ctx->scratch) + 256);
+  constexpr int xm = SPMM_SGRP_XM;  // groups per XCD chunk
+  // a shallow grid (a few waves per resident slot): groups longest first (reddit bs 8
+  // 1.50 -> 1.37 ms: 2.4 waves per slot, group loads up to 2.7x the mean), else the
+  // XCD-chunked order
+  const int* ord = nullptr;
+  dim3 lgrid = grid;
+  const long slots = 12L * ctx->num_cus;
+  if (SPMM_SGRP_LPT && (long)ngroups * grid.y <= kLptRounds * slots) {
+    // chunks of xm groups, longest first (block_row_order_kernel keyed by a chunk's blocks)
+    // (chunks of xm groups ranked together, XCD chunks kept: 1.41-1.43 ms on reddit bs 8
+    // against 1.37 for single groups, the same box; profiles/r05b/small_grp/)
+    const int cx = SPMM_SGRP_LPT == 2 ? xm : 1;
+    const int nch = (ngroups + cx - 1) / cx;
+    if (spmm_status_t st = spmm::ensure_order_buffer(ctx, nch)) return st;
+    const double mean = (double)a.nnzb / nch;
+    int gshift = 0;
+    while ((4.0 * mean) / (1 << gshift) > 1023.0) ++gshift;
+    hipLaunchKernelGGL(block_row_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, nch,
+                       a.rowptr, nullptr, a.mb, 0, ctx->order, 32 / bs * cx, gshift);
+    ord = ctx->order;
+    lgrid.x = nch * cx;
+  }
+  ctx->small_path = 1;  // the probe's sums decide (spmm_bsr_small_path)
+  ctx->small_path_bs = bs;
+  if (hipError_t e = hipMemsetAsync(stat, 0, 2 * sizeof(*stat), ctx->stream))
+    return spmm::from_hip(e);
+  const dim3 pgrid(std::min(ngroups, 1024));
+  spmm::with_int<2, 4, 8>(bs, [&](auto bs_) {
+    constexpr int BS = decltype(bs_)::value;
+    hipLaunchKernelGGL(small_grp_probe_kernel<BS>, pgrid, dim3(64), 0, ctx->stream, a.mb, ngroups,
+                       a.rowptr, a.colind, stat);
+    spmm::with_bools(
+        [&](auto rd, auto cr) {
+          hipLaunchKernelGGL((bsr_small_grp_kernel<BS, decltype(rd)::value, decltype(cr)::value>),
+                             lgrid, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind,
+                             a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc,
+                             SPMM_SGRP_LPT != 2 && ord ? 1 : xm, dirty, ord, a.nnzb, stat);
+        },
+        a.rowd, a.crow);
+  });
+  // the tiles it flagged (a non-finite B value met): bsr_small_kernel recomputes them
+  // (n % 4 == 0, ldb % 2 == 0 and B 8-B aligned: small_grouped_ok)
+  launch_small(a, a.n > 64, 8, dirty, (int)grid.y);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 2 / 4 / 8, the lane-group VALU kernel: 2 floats per lane when B allows 8-B gathers;
+// XCD chunks of 8 workgroups (32 block rows; TUNING builds: SPMM_SMALL_XM).
+spmm_status_t small_valu(const BsrArgs<float>& a) {
+  a.ctx->small_path = 0;
+  const bool v2 = a.n > 64 && a.n % 2 == 0 && a.ldb % 2 == 0 && aligned(a.B, 8);
+  launch_small(a, v2, tuning_env_int("SPMM_SMALL_XM", 8));
+  return SPMM_STATUS_SUCCESS;
+}
+
+// Any other block size or layout: the VALU kernel.
+template <typename T>
+spmm_status_t generic(const BsrArgs<T>& a) {
+  const dim3 grid(a.mb, (a.n + 63) / 64);
+  hipLaunchKernelGGL(bsr_generic_kernel<T>, grid, dim3(256), 0, a.ctx->stream, a.mb, a.n, a.bs,
+                     a.rowd, a.rowptr, a.colind, a.val, a.B, a.ldb, a.brow, a.alpha, a.beta, a.C,
+                     a.ldc, a.crow);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 16 fp16, column-masked (bsr16_cm_kernel, at least 8 waves per SIMD): below 128
+// columns, and kBsr16F16Cm.
+spmm_status_t bs16_f16_column_masked(const BsrArgs<_Float16>& a) {
+  const dim3 grid(a.mb, (a.n + 255) / 256);
+  spmm::with_bools(
+      [&](auto cr) {
+        hipLaunchKernelGGL((bsr16_cm_kernel<_Float16, decltype(cr)::value, 2, 5, 8>), grid,
+                           dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
+                           a.ldb, a.alpha, a.beta, a.C, a.ldc);
+      },
+      a.crow);
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 16 fp16 column stream: kBsr16F16Cs, kBsr16F16CsNoNt (no nt A copies), or the analysed
+// form (msk). TUNING builds: SPMM_CS16_TT puts a block row's column tiles together.
+spmm_status_t bs16_f16_column_stream(const BsrArgs<_Float16>& a, bool msk, int lv) {
+  spmm_context* ctx = a.ctx;
+  const dim3 gc(a.mb, (a.n + 255) / 256);
+  const int* ord = nullptr;
+  if (spmm_status_t st = block_row_order(ctx, a.mb, gc.y, a.rowptr, &ord)) return st;
+  const int ntt = tuning_env_int("SPMM_CS16_TT", 0) && gc.y > 1 ? (int)gc.y : 0;
+  const dim3 gg = ntt ? dim3((unsigned)(8 * ((a.mb + 7) / 8) * ntt), 1) : gc;
+  auto stream = [&](auto ant, auto mk) {
+    spmm::with_bools(
+        [&](auto cr) {
+          hipLaunchKernelGGL((bsr16_f16_cs_kernel<decltype(cr)::value, 2, 4, 0, 48,
+                                                  decltype(ant)::value, true, 256,
+                                                  decltype(mk)::value>),
+                             gg, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val,
+                             a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, a.masks, ntt);
+        },
+        a.crow);
+  };
+  if (msk) stream(std::true_type{}, std::true_type{});
+  else if (lv == kBsr16F16Cs) stream(std::true_type{}, std::false_type{});
+  else stream(std::false_type{}, std::false_type{});
+  return SPMM_STATUS_SUCCESS;
+}
+
+// bs 16 fp16 on the copy kernels: which of the two, and the stream's variant.
+spmm_status_t bs16_f16_copy(const BsrArgs<_Float16>& a, bool msk) {
+  const int var = variant_override();
+  int lv = a.n >= 128 ? kBsr16F16Cs : kBsr16F16Cm;
+  if (var == kBsr16F16Cm || (a.n >= 128 && (var == kBsr16F16Cs || var == kBsr16F16CsNoNt)))
+    lv = var;
+  if (msk) lv = kBsr16F16Cs;  // COLUMN blocks: only the analysed stream reads them here
+  return lv == kBsr16F16Cm ? bs16_f16_column_masked(a) : bs16_f16_column_stream(a, msk, lv);
+}
+
+// The values a TUNING build's SPMM_GRP32_VARIANT / SPMM_GRP_VARIANT accept, as digits:
+// stages P * 10 + occupancy hint OCC; + 200: two items per barrier (IPB 2); + 1000:
+// fragments through LDS (AL); 933: the no-MFMA diagnostic (wrong results). Any other
+// value, and every release build: 33. f gets the value as an integral constant.
+// (4, 4) with two items per barrier is not offered: at W = 4 the allocator spills the A
+// fragments in flight (tools/isa_vmcnt.py --inflight). (3, 4) spilled with the vector row
+// loads (and faulted); with the scalar ones it audits clean
+// (every TUNING build is audited before it runs: tools/build_tuning.sh)
+template <typename F>
+void with_grp32_variant(F&& f) {
+#ifdef SPMM_TUNING
+  if (spmm::with_int<30, 32, 34, 42, 43, 44, 52, 53, 933>(
+          tuning_env_int("SPMM_GRP32_VARIANT", 0), f))
+    return;
+#endif
+  f(std::integral_constant<int, 33>{});
+}
+template <typename F>
+void with_grp16_variant(F&& f) {
+#ifdef SPMM_TUNING
+  if (spmm::with_int<30, 32, 42, 43, 52, 53, 23, 24, 243, 262, 263, 1033, 1043, 34>(
+          tuning_env_int("SPMM_GRP_VARIANT", 0), f))
+    return;
+#endif
+  f(std::integral_constant<int, 33>{});
+}
+// groups per XCD chunk: chunks of 32 block rows (TUNING builds: SPMM_GRP_XM)
+int grp_xm(int W) {
+  const int env = tuning_env_int("SPMM_GRP_XM", -1);
+  return env >= 0 ? env : 32 / W;
+}
 
 }  // namespace
 
@@ -4092,14 +4515,7 @@ spmm_status_t launch_bsrmm_f32(spmm_context* ctx, spmm_direction_t dir, int mb, 
                                const int* colind, const float* val, const float* B, int ldb,
                                spmm_order_t orderB, float beta, float* C, int ldc,
                                spmm_order_t orderC, bool dense_blocks, const unsigned* masks) {
-  (void)kb;
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const bool rowd = dir == SPMM_DIRECTION_ROW;
-  const bool brow = orderB == SPMM_ORDER_ROW;
-  const bool crow = orderC == SPMM_ORDER_ROW;
-  const bool vec_ok = aligned(val, 16) && (brow || (aligned(B, 16) && ldb % 4 == 0));
-  const int slot = timing_begin(ctx);
-  const int var = variant_override();
   // SPMM_BSR_DENSE_BLOCK_PRODUCT: cusparseSbsrmm's dense-block semantics, the full-panel
   // kernels only (no column masks); the split-bf16 option stays the hybrid's own
   const bool hybrid_part = dense_blocks;
@@ -4108,373 +4524,23 @@ spmm_status_t launch_bsrmm_f32(spmm_context* ctx, spmm_direction_t dir, int mb, 
     dense_blocks = true;
     masks = nullptr;
   }
-  // the column stream stores row-major C as 16-B row pieces (and its segment fix-up too):
-  // C and ldc must keep them aligned, else the fragment kernel's scalar stores serve
-  const bool c16 = !crow || (aligned(C, 16) && ldc % 4 == 0);
-  // the analysed column stream: COLUMN blocks with their column masks
-  const bool msk = masks && bs == 32 && !rowd && !dense_blocks && c16;
-  if (bs == 32 && (rowd || msk) && brow && n >= 4 && n % 4 == 0 && ldb % 4 == 0 &&
-      aligned(val, 16) && aligned(B, 16) && (dense_blocks || c16)) {
-    const dim3 grid(mb, (n + 127) / 128);
-    const bool narrow = (size_t)ldb * 128 < (1u << 31);  // 32-row panels addressable in 31 bits
-    int lv = dense_blocks ? kBsr32Dense : kBsr32Cs;
-    // (a tuning override never replaces the dense-block kernel)
-    if (!dense_blocks && (var == kBsr32CsNoNt || var == kBsr32CsWideLdb || var == kBsr32Cs))
-      lv = var;
-    if (!narrow && (lv == kBsr32Cs || lv == kBsr32CsNoNt)) lv = kBsr32CsWideLdb;
-    if (lv == kBsr32Dense) {
-      // split-bf16 (opt-in, SPMM_HYBRID_SPLIT_BF16): wave-pair split-K for row-major C
-      // (products hybrid 1.86-1.87 vs 1.89 ms fused, reddit 0.80 vs 0.83,
-      // profiles/r01_hybrid_split.jsonl), one k range per wave for column-major C
-      const bool split = hybrid_part && (ctx->hybrid_flags & SPMM_HYBRID_SPLIT_BF16);
-      if (split && crow)
-        hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32, false, 24, true, true>), grid,
-                           dim3(256), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha,
-                           beta, C, ldc, nullptr, nullptr, nullptr, 0, nullptr);
-      else if (split)
-        hipLaunchKernelGGL((bsr32_f32_lds_kernel<false, 2, 32, false, 24, true>), grid,
-                           dim3(256), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha,
-                           beta, C, ldc, nullptr, nullptr, nullptr, 0, nullptr);
-      else if (crow)
-        hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32>), grid, dim3(256), 0, ctx->stream,
-                           mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, nullptr,
-                           nullptr, nullptr, 0, nullptr);
-      else
-        hipLaunchKernelGGL((bsr32_f32_lds_kernel<false, 2, 32>), grid, dim3(256), 0, ctx->stream,
-                           mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, nullptr,
-                           nullptr, nullptr, 0, nullptr);
-    } else {
-      // the column stream: segments of outlier rows (row-major C, shallow grids) or the
-      // longest-first order (shallow grids), else the XCD-chunked order
-      const int* ord = nullptr;
-      const int4 *sg = nullptr, *spl = nullptr;
-      float* pt = nullptr;
-      int nsg = 0, nspl = 0;
-      spmm_status_t st = SPMM_STATUS_SUCCESS;
-      if (crow) st = cs2_segments(ctx, mb, nnzb, grid.y, rowptr, &sg, &spl, &pt, &nsg, &nspl);
-      if (st == SPMM_STATUS_SUCCESS && !sg) st = block_row_order(ctx, mb, grid.y, rowptr, &ord);
-      if (st != SPMM_STATUS_SUCCESS) {
-        timing_end(ctx, slot);
-        return st;
-      }
-      const dim3 g2(sg ? nsg : mb, grid.y);
-      // n <= 64: the 64-column tile (C64; grid.y is 1 either way, so the segments'
-      // partial layout is the same)
-      const bool c64 = n <= 64;
-      // the panel stream (same bits) when the probe finds the blocks dense: both kernels go
-      // out, the probe's sums choose on the device (no host round trip, graph-capturable)
-      unsigned long long* pstat = nullptr;
-      if (!msk && !sg && lv == kBsr32Cs && nnzb >= kPanelMinBlocks) {
-        if (spmm_status_t st2 = spmm::ensure_scratch(ctx, 2 * sizeof(unsigned long long))) {
-          timing_end(ctx, slot);
-          return st2;
-        }
-        pstat = static_cast<unsigned long long*>(ctx->scratch);
-        if (hipError_t e = hipMemsetAsync(pstat, 0, 2 * sizeof(*pstat), ctx->stream)) {
-          timing_end(ctx, slot);
-          return from_hip(e);
-        }
-        const int ns = std::min(nnzb, kPanelSamples);
-        hipLaunchKernelGGL(panel_probe_kernel, dim3((ns + 4 * kPanelPerWave - 1) / (4 * kPanelPerWave)),
-                           dim3(256), 0, ctx->stream, (long long)nnzb, ns, 0, val, pstat);
-      }
-#define CS2_ONE(C64_, O32_, PK_, ANT_)                                                           \
-  do {                                                                                           \
-    if (crow)                                                                                    \
-      hipLaunchKernelGGL((bsr32_f32_cs2_kernel<true, 32, 6, 3, O32_, PK_, ANT_, false, false,    \
-                                               C64_>),                                           \
-                         g2, dim3(64), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb,       \
-                         alpha, beta, C, ldc, ord, sg, pt, masks, pstat);                        \
-    else                                                                                         \
-      hipLaunchKernelGGL((bsr32_f32_cs2_kernel<false, 32, 6, 3, O32_, PK_, ANT_, false, false,   \
-                                               C64_>),                                           \
-                         g2, dim3(64), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb,       \
-                         alpha, beta, C, ldc, ord, nullptr, nullptr, masks, pstat);              \
-  } while (0)
-#define CS2_LAUNCH(O32_, PK_, ANT_)                                                              \
-  do {                                                                                           \
-    if (c64) CS2_ONE(true, O32_, PK_, ANT_);                                                     \
-    else CS2_ONE(false, O32_, PK_, ANT_);                                                        \
-  } while (0)
-#define MSK_ONE(C64_, O32_)                                                                      \
-  do {                                                                                           \
-    if (crow)                                                                                    \
-      hipLaunchKernelGGL((bsr32_f32_cs2_kernel<true, 32, 6, 3, O32_, true, true, true, false,    \
-                                               C64_>),                                           \
-                         g2, dim3(64), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb,       \
-                         alpha, beta, C, ldc, ord, sg, pt, masks);                               \
-    else                                                                                         \
-      hipLaunchKernelGGL((bsr32_f32_cs2_kernel<false, 32, 6, 3, O32_, true, true, true, false,   \
-                                               C64_>),                                           \
-                         g2, dim3(64), 0, ctx->stream, mb, n, rowptr, colind, val, B, ldb,       \
-                         alpha, beta, C, ldc, ord, nullptr, nullptr, masks);                     \
-  } while (0)
-#define MSK_LAUNCH(O32_)                                                                         \
-  do {                                                                                           \
-    if (c64) MSK_ONE(true, O32_);                                                                \
-    else MSK_ONE(false, O32_);                                                                   \
-  } while (0)
-      // (4, 8 or 10 items in flight: 2.11-2.15 / 2.11-2.12 / 2.43 ms against 2.11 at 6 on
-      // the products stand-in, profiles/r03_analysed_sweep.txt)
-      if (msk && narrow) MSK_LAUNCH(true);
-      else if (msk) MSK_LAUNCH(false);
-#undef MSK_LAUNCH
-#undef MSK_ONE
-      else if (lv == kBsr32Cs) CS2_LAUNCH(true, true, true);
-      else if (lv == kBsr32CsNoNt) CS2_LAUNCH(true, true, false);
-      else CS2_LAUNCH(false, true, true);  // kBsr32CsWideLdb
-#undef CS2_LAUNCH
-#undef CS2_ONE
-      if (pstat) {
-        if (crow && c64)
-          hipLaunchKernelGGL((bsr32_f32_panel_kernel<true, true, SPMM_PANEL_D64>), g2, dim3(64), 0, ctx->stream,
-                             mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, ord, pstat);
-        else if (crow)
-          hipLaunchKernelGGL((bsr32_f32_panel_kernel<true, false, SPMM_PANEL_D128>), g2, dim3(64), 0,
-                             ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc,
-                             ord, pstat);
-        else if (c64)
-          hipLaunchKernelGGL((bsr32_f32_panel_kernel<false, true, SPMM_PANEL_D64>), g2, dim3(64), 0,
-                             ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc,
-                             ord, pstat);
-        else
-          hipLaunchKernelGGL((bsr32_f32_panel_kernel<false, false, SPMM_PANEL_D128>), g2, dim3(64), 0,
-                             ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc,
-                             ord, pstat);
-      }
-      if (spl)
-        hipLaunchKernelGGL(seg_fixup_kernel, dim3(nspl, grid.y), dim3(256), 0, ctx->stream, n,
-                           spl, pt, alpha, beta, C, ldc);
-    }
-  } else if (bs == 64 && rowd && brow && n >= 4 && n % 4 == 0 && ldb % 4 == 0 &&
-             aligned(val, 16) && aligned(B, 16) && c16 && !dense_sem) {
-    // bs 64: the bs 32 column stream on the four 32 x 32 sub-blocks of each block
-    // (SUB), one wave per 32-row half of a block row and 128 columns
-    const int mb2 = 2 * mb;
-    const dim3 g2(mb2, (n + 127) / 128);
-    const bool narrow = (size_t)ldb * 128 < (1u << 31);
-    const int* ord = nullptr;
-    if (const spmm_status_t st = block_row_order(ctx, mb2, g2.y, rowptr, &ord, 12, nullptr, 0, 1)) {
-      timing_end(ctx, slot);
-      return st;
-    }
-    // the panel stream over the sub-blocks when the probe finds them dense (same bits)
-    unsigned long long* pstat = nullptr;
-    if (narrow && 4LL * nnzb >= kPanelMinBlocks) {
-      if (spmm_status_t st2 = spmm::ensure_scratch(ctx, 2 * sizeof(unsigned long long))) {
-        timing_end(ctx, slot);
-        return st2;
-      }
-      pstat = static_cast<unsigned long long*>(ctx->scratch);
-      if (hipError_t e = hipMemsetAsync(pstat, 0, 2 * sizeof(*pstat), ctx->stream)) {
-        timing_end(ctx, slot);
-        return from_hip(e);
-      }
-      const long long nsub = 4LL * nnzb;
-      const int ns = (int)std::min<long long>(nsub, kPanelSamples);
-      hipLaunchKernelGGL(panel_probe_kernel, dim3((ns + 4 * kPanelPerWave - 1) / (4 * kPanelPerWave)),
-                         dim3(256), 0, ctx->stream, nsub, ns, 1, val, pstat);
-    }
-#define SUB_ONE(CR_, O32_, C64_)                                                                 \
-  hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR_, 32, 6, 3, O32_, true, true, false, true, C64_>),  \
-                     g2, dim3(64), 0, ctx->stream, mb2, n, rowptr, colind, val, B, ldb, alpha,   \
-                     beta, C, ldc, ord, nullptr, nullptr, nullptr, pstat)
-#define SUB_LAUNCH(CR_, O32_)                                                                    \
-  do {                                                                                           \
-    if (n <= 64) SUB_ONE(CR_, O32_, true);  /* the 64-column tile */                             \
-    else SUB_ONE(CR_, O32_, false);                                                              \
-  } while (0)
-    if (crow) {
-      if (narrow) SUB_LAUNCH(true, true); else SUB_LAUNCH(true, false);
-    } else {
-      if (narrow) SUB_LAUNCH(false, true); else SUB_LAUNCH(false, false);
-    }
-#undef SUB_LAUNCH
-#undef SUB_ONE
-    if (pstat) {
-#define PSUB(CR_, C64_, D_)                                                                       \
-  hipLaunchKernelGGL((bsr32_f32_panel_kernel<CR_, C64_, D_, true>), g2, dim3(64), 0, ctx->stream, \
-                     mb2, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, ord, pstat)
-      if (crow && n <= 64) PSUB(true, true, SPMM_PANEL_D64);
-      else if (crow) PSUB(true, false, SPMM_PANEL_D128);
-      else if (n <= 64) PSUB(false, true, SPMM_PANEL_D64);
-      else PSUB(false, false, SPMM_PANEL_D128);
-#undef PSUB
-    }
-  } else if (bs == 32 && vec_ok) {
-    const int waves = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
-    dim3 grid(mb, (n + 32 * waves - 1) / (32 * waves));
-    SPMM_BSR_DISPATCH(bsr32_f32_mfma_kernel, SPMM_COMMA kBsr32Default, grid, dim3(64 * waves),
-                      ctx->stream, rowd, brow, crow, mb, n, rowptr, colind, val, B, ldb, alpha,
-                      beta, C, ldc);
-  } else if (bs == 16 && rowd && brow && n >= 4 && n % 4 == 0 && ldb % 4 == 0 &&
-             aligned(val, 16) && aligned(B, 16) && !dense_sem) {
-    // output columns per workgroup: 256, or the narrower tile a small n fills (at n = 64
-    // a 256-column tile left 3 of its 4 waves idle: reference sweep, profiles/r05_sweep/)
-    const int cols = n <= 64 ? 64 : (n <= 128 ? 128 : 256);
-    const dim3 grid(mb, (n + cols - 1) / cols);
-#define CM16_LAUNCH(CR_, COLS_)                                                                   \
-  hipLaunchKernelGGL((bsr16_cm_kernel<float, CR_, 2, 5, 1, COLS_>), grid, dim3(256), 0,           \
-                     ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc)
-    if (cols == 64) {
-      if (crow) CM16_LAUNCH(true, 64); else CM16_LAUNCH(false, 64);
-    } else if (cols == 128) {
-      if (crow) CM16_LAUNCH(true, 128); else CM16_LAUNCH(false, 128);
-    } else {
-      if (crow) CM16_LAUNCH(true, 256); else CM16_LAUNCH(false, 256);
-    }
-#undef CM16_LAUNCH
-  } else if (bs == 16 && vec_ok) {
-    const int waves = n <= 64 ? 1 : (n <= 128 ? 2 : 4);
-    dim3 grid(mb, (n + 64 * waves - 1) / (64 * waves));
-    SPMM_BSR_DISPATCH(bsr16_f32_mfma_kernel, SPMM_COMMA kBsr16Default, grid, dim3(64 * waves),
-                      ctx->stream, rowd, brow, crow, mb, n, rowptr, colind, val, B, ldb, alpha,
-                      beta, C, ldc);
-  } else if ((bs == 2 || bs == 4 || bs == 8) && brow && !dense_sem && nnzb > 0 && n >= 4 &&
-             n % 4 == 0 && ldb % 2 == 0 && aligned(B, 8) && aligned(val, 16) &&
-             (!crow || (ldc % 4 == 0 && aligned(C, 16))) && kb < (1 << 26) &&
-             (size_t)ldb * bs * 4 < (1u << 31) && (size_t)(32 / bs) * kb * bs * bs * 4 < (1u << 31) &&
-             (nnzb >= (1 << 20) || (ctx->bsr_flags & SPMM_BSR_SMALL_GROUPED)) &&
-             small_grp_enabled()) {
-    // (from 2^20 blocks: its fixed cost, the probe and the order, about 40 us, made the
-    // reference sweep's small cells up to 2x slower; SPMM_BSR_SMALL_GROUPED forces it)
-    // the grouped MFMA stream: 32 / bs block rows per wave share each B row of their union
-    const int ngroups = (mb + 32 / bs - 1) / (32 / bs);
-    const dim3 grid(ngroups, (n + 127) / 128);
-    if (spmm_status_t st = ensure_scratch(ctx, (size_t)ngroups * grid.y * sizeof(int) + 256)) {
-      timing_end(ctx, slot);
-      return st;
-    }
-    // the probe's integer sums
-    unsigned long long* stat = static_cast<unsigned long long*>(ctx->scratch);
-    int* dirty = reinterpret_cast<int*>(static_cast<char*>(ctx->scratch) + 256);
-    constexpr int xm = SPMM_SGRP_XM;  // groups per XCD chunk
-    // a shallow grid (a few waves per resident slot): groups longest first (reddit bs 8
-    // 1.50 -> 1.37 ms: 2.4 waves per slot, group loads up to 2.7x the mean), else the
-    // XCD-chunked order
-    const int* ord = nullptr;
-    dim3 lgrid = grid;
-    {
-      const long slots = 12L * ctx->num_cus;
-      if (SPMM_SGRP_LPT && (long)ngroups * grid.y <= kLptRounds * slots) {
-        // chunks of xm groups, longest first (block_row_order_kernel keyed by a chunk's blocks)
-        // (chunks of xm groups ranked together, XCD chunks kept: 1.41-1.43 ms on reddit bs 8
-        // against 1.37 for single groups, the same box; profiles/r05b/small_grp/)
-        const int cx = SPMM_SGRP_LPT == 2 ? xm : 1;
-        const int nch = (ngroups + cx - 1) / cx;
-        if (spmm_status_t st = spmm::ensure_order_buffer(ctx, nch)) {
-          timing_end(ctx, slot);
-          return st;
-        }
-        const double mean = (double)nnzb / nch;
-        int gshift = 0;
-        while ((4.0 * mean) / (1 << gshift) > 1023.0) ++gshift;
-        hipLaunchKernelGGL(block_row_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, nch,
-                           rowptr, nullptr, mb, 0, ctx->order, 32 / bs * cx, gshift);
-        ord = ctx->order;
-        lgrid.x = nch * cx;
-      }
-    }
-#define SGRP_ONE(BS_, RD_, CR_)                                                                  \
-  hipLaunchKernelGGL((bsr_small_grp_kernel<BS_, RD_, CR_>), lgrid, dim3(64), 0, ctx->stream, mb, \
-                     n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, SPMM_SGRP_LPT != 2 && ord ? 1 : xm, dirty, ord, nnzb, \
-                     stat)
-#define SGRP_LAUNCH(BS_)                                                                         \
-  do {                                                                                           \
-    if (rowd && crow) SGRP_ONE(BS_, true, true);                                                 \
-    else if (rowd) SGRP_ONE(BS_, true, false);                                                   \
-    else if (crow) SGRP_ONE(BS_, false, true);                                                   \
-    else SGRP_ONE(BS_, false, false);                                                            \
-  } while (0)
-    ctx->small_path = 1;  // the probe's sums decide (spmm_bsr_small_path)
-    ctx->small_path_bs = bs;
-    // the choice per matrix first (small_grp_probe_kernel), then the stream
-    if (hipError_t e = hipMemsetAsync(stat, 0, 2 * sizeof(*stat), ctx->stream)) {
-      timing_end(ctx, slot);
-      return from_hip(e);
-    }
-    const dim3 pgrid(std::min(ngroups, 1024));
-    if (bs == 8)
-      hipLaunchKernelGGL(small_grp_probe_kernel<8>, pgrid, dim3(64), 0, ctx->stream, mb, ngroups,
-                         rowptr, colind, stat);
-    else if (bs == 4)
-      hipLaunchKernelGGL(small_grp_probe_kernel<4>, pgrid, dim3(64), 0, ctx->stream, mb, ngroups,
-                         rowptr, colind, stat);
-    else
-      hipLaunchKernelGGL(small_grp_probe_kernel<2>, pgrid, dim3(64), 0, ctx->stream, mb, ngroups,
-                         rowptr, colind, stat);
-    if (bs == 8) SGRP_LAUNCH(8);
-    else if (bs == 4) SGRP_LAUNCH(4);
-    else SGRP_LAUNCH(2);
-#undef SGRP_LAUNCH
-#undef SGRP_ONE
-    // the tiles it flagged (a non-finite B value met): bsr_small_kernel recomputes them
-    const bool v2 = n > 64;  // n % 4 == 0, ldb % 2 == 0 and B 8-B aligned above
-    const dim3 fgrid((mb + 3) / 4, (n + (v2 ? 127 : 63)) / (v2 ? 128 : 64));
-#define SFIX_ONE(BS_, V_, RD_, CR_)                                                              \
-  hipLaunchKernelGGL((bsr_small_kernel<BS_, V_, RD_, CR_>), fgrid, dim3(256), 0, ctx->stream, mb, \
-                     n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, 8, dirty, (int)grid.y)
-#define SFIX_LAUNCH(BS_, V_)                                                                     \
-  do {                                                                                           \
-    if (rowd && crow) SFIX_ONE(BS_, V_, true, true);                                             \
-    else if (rowd) SFIX_ONE(BS_, V_, true, false);                                               \
-    else if (crow) SFIX_ONE(BS_, V_, false, true);                                               \
-    else SFIX_ONE(BS_, V_, false, false);                                                        \
-  } while (0)
-    if (bs == 8) {
-      if (v2) SFIX_LAUNCH(8, 2); else SFIX_LAUNCH(8, 1);
-    } else if (bs == 4) {
-      if (v2) SFIX_LAUNCH(4, 2); else SFIX_LAUNCH(4, 1);
-    } else {
-      if (v2) SFIX_LAUNCH(2, 2); else SFIX_LAUNCH(2, 1);
-    }
-#undef SFIX_LAUNCH
-#undef SFIX_ONE
-  } else if ((bs == 2 || bs == 4 || bs == 8) && brow && !dense_sem) {
-    ctx->small_path = 0;
-    // the lane-group VALU kernel: 2 floats per lane when B allows 8-B gathers
-    const bool v2 = n > 64 && n % 2 == 0 && ldb % 2 == 0 && aligned(B, 8);
-    const dim3 grid((mb + 3) / 4, (n + (v2 ? 127 : 63)) / (v2 ? 128 : 64));
-    // XCD chunks of 8 workgroups (32 block rows; TUNING builds: SPMM_SMALL_XM)
-#ifdef SPMM_TUNING
-    static const int xm = [] {
-      const char* e = getenv("SPMM_SMALL_XM");
-      return e ? atoi(e) : 8;
-    }();
-#else
-    constexpr int xm = 8;
-#endif
-#define SMALL_ONE(BS_, V_, RD_, CR_)                                                             \
-  hipLaunchKernelGGL((bsr_small_kernel<BS_, V_, RD_, CR_>), grid, dim3(256), 0, ctx->stream, mb, \
-                     n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc, xm)
-#define SMALL_LAUNCH(BS_, V_)                                                                    \
-  do {                                                                                           \
-    if (rowd && crow) SMALL_ONE(BS_, V_, true, true);                                            \
-    else if (rowd) SMALL_ONE(BS_, V_, true, false);                                              \
-    else if (crow) SMALL_ONE(BS_, V_, false, true);                                              \
-    else SMALL_ONE(BS_, V_, false, false);                                                       \
-  } while (0)
-    if (bs == 8) {
-      if (v2) SMALL_LAUNCH(8, 2); else SMALL_LAUNCH(8, 1);
-    } else if (bs == 4) {
-      if (v2) SMALL_LAUNCH(4, 2); else SMALL_LAUNCH(4, 1);
-    } else {
-      if (v2) SMALL_LAUNCH(2, 2); else SMALL_LAUNCH(2, 1);
-    }
-#undef SMALL_LAUNCH
-#undef SMALL_ONE
-  } else {
-    dim3 grid(mb, (n + 63) / 64);
-    hipLaunchKernelGGL(bsr_generic_kernel<float>, grid, dim3(256), 0, ctx->stream, mb, n, bs,
-                       rowd, rowptr, colind, val, B, ldb, brow, alpha, beta, C, ldc, crow);
-  }
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  const BsrArgs<float> a{ctx, mb, kb, n, nnzb, bs, alpha, rowptr, colind, val, B, ldb, beta, C, ldc,
+                         dir == SPMM_DIRECTION_ROW, orderB == SPMM_ORDER_ROW,
+                         orderC == SPMM_ORDER_ROW, masks};
+  return timed(ctx, [&] {
+    if (bs32_copy_kernels(a, dense_blocks)) return bs32_copy(a, dense_blocks, hybrid_part);
+    if (bs64_sub_stream_ok(a, dense_sem)) return bs64_sub_stream(a);
+    if (bs == 32 && fragments_loadable(val, a.brow, B, ldb, 4)) return fragment_fallback(a);
+    if (bs16_column_masked_ok(a, dense_sem)) return bs16_column_masked(a);
+    if (bs == 16 && fragments_loadable(val, a.brow, B, ldb, 4)) return fragment_fallback(a);
+    if (small_grouped_ok(a, dense_sem)) return small_grouped(a);
+    if (small_valu_ok(a, dense_sem)) return small_valu(a);
+    return generic(a);
+  });
 }
 
 bool hybrid32_fusable(int n, int ldb, int ldc, const float* bval, const float* B, const float* C) {
-  return n >= 4 && n % 4 == 0 && ldb % 4 == 0 && ldc % 2 == 0 && aligned(bval, 16) &&
-         aligned(B, 16) && aligned(C, 8);
+  return b_rows_copyable(n, ldb, bval, B, 4) && ldc % 2 == 0 && aligned(C, 8);
 }
 
 spmm_status_t launch_hybrid32_fused(spmm_context* ctx, int m, int n, float alpha,
@@ -4483,24 +4549,25 @@ spmm_status_t launch_hybrid32_fused(spmm_context* ctx, int m, int n, float alpha
                                     const float* B, int ldb, float beta, float* C, int ldc) {
   const int mb = (m + 31) / 32;
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const int slot = timing_begin(ctx);
-  const dim3 grid(mb, (n + 127) / 128);
-  // longest first (blocks and remainder entries) when the grid is a few
-  // workgroups per slot deep (4 workgroups per CU)
-  const int* ord = nullptr;
-  if (const spmm_status_t st = block_row_order(ctx, mb, grid.y, brp, &ord, 4, crp, m)) {
-    timing_end(ctx, slot);
-    return st;
-  }
-  if (ctx->hybrid_flags & SPMM_HYBRID_SPLIT_BF16)  // wave-pair split-K, split-bf16 products
-    hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32, true, 24, true, true>), grid, dim3(256), 0,
-                       ctx->stream, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc, crp, cci, cv, m, ord);
-  else  // D = 2 and 24 remainder gathers in flight (73 VGPRs): 4 workgroups per CU.
-        // Products stand-in 2.09 ms vs 2.42 with 32 in flight and 2.81 with D = 3.
-    hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32, true, 24>), grid, dim3(256), 0,
-                       ctx->stream, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc, crp, cci, cv, m, ord);
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return timed(ctx, [&] {
+    const dim3 grid(mb, (n + 127) / 128);
+    // longest first (blocks and remainder entries) when the grid is a few
+    // workgroups per slot deep (4 workgroups per CU)
+    const int* ord = nullptr;
+    if (spmm_status_t st = block_row_order(ctx, mb, grid.y, brp, &ord, 4, crp, m)) return st;
+    // D = 2 and 24 remainder gathers in flight (73 VGPRs): 4 workgroups per CU.
+    // Products stand-in 2.09 ms vs 2.42 with 32 in flight and 2.81 with D = 3.
+    // SPMM_HYBRID_SPLIT_BF16: wave-pair split-K, split-bf16 products
+    with_bools(
+        [&](auto sp) {
+          constexpr bool SP = decltype(sp)::value;
+          hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32, true, 24, SP, SP>), grid, dim3(256),
+                             0, ctx->stream, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc,
+                             crp, cci, cv, m, ord);
+        },
+        (ctx->hybrid_flags & SPMM_HYBRID_SPLIT_BF16) != 0);
+    return SPMM_STATUS_SUCCESS;
+  });
 }
 
 spmm_status_t launch_bsrmm_f16(spmm_context* ctx, spmm_direction_t dir, int mb, int kb, int n,
@@ -4508,146 +4575,42 @@ spmm_status_t launch_bsrmm_f16(spmm_context* ctx, spmm_direction_t dir, int mb, 
                                const int* colind, const uint16_t* val16, const uint16_t* B16,
                                int ldb, spmm_order_t orderB, float beta, float* C, int ldc,
                                spmm_order_t orderC, const unsigned* masks) {
-  (void)kb;
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const _Float16* val = reinterpret_cast<const _Float16*>(val16);
-  const _Float16* B = reinterpret_cast<const _Float16*>(B16);
-  const bool rowd = dir == SPMM_DIRECTION_ROW;
-  const bool brow = orderB == SPMM_ORDER_ROW;
-  const bool crow = orderC == SPMM_ORDER_ROW;
-  const bool vec_ok = aligned(val, 16) && (brow || (aligned(B, 16) && ldb % 8 == 0));
-  const int slot = timing_begin(ctx);
-  const int var = variant_override();
+  const BsrArgs<_Float16> a{ctx, mb, kb, n, nnzb, bs, alpha, rowptr, colind,
+                            reinterpret_cast<const _Float16*>(val16),
+                            reinterpret_cast<const _Float16*>(B16), ldb, beta, C, ldc,
+                            dir == SPMM_DIRECTION_ROW, orderB == SPMM_ORDER_ROW,
+                            orderC == SPMM_ORDER_ROW, masks};
   // SPMM_BSR_DENSE_BLOCK_PRODUCT: the register-fragment kernel (dense blocks, no masks)
   const bool dense_sem = (ctx->bsr_flags & SPMM_BSR_DENSE_BLOCK_PRODUCT) != 0;
-  // the analysed column stream: COLUMN blocks with their column masks, n >= 128
-  const bool msk = masks && bs == 16 && !rowd && n >= 128 && !dense_sem;
-  if (bs == 16 && (rowd || msk) && brow && n >= 8 && n % 8 == 0 && ldb % 8 == 0 &&
-      aligned(val, 16) && aligned(B, 16) && !dense_sem) {
-    int lv = n >= 128 ? kBsr16F16Cs : kBsr16F16Cm;
-    if (var == kBsr16F16Cm ||
-        (n >= 128 && (var == kBsr16F16Cs || var == kBsr16F16CsNoNt)))
-      lv = var;
-    if (msk) lv = kBsr16F16Cs;  // COLUMN blocks: only the analysed stream reads them here
-    if (lv == kBsr16F16Cm) {
-      const dim3 grid(mb, (n + 255) / 256);
-      if (crow)
-        hipLaunchKernelGGL((bsr16_cm_kernel<_Float16, true, 2, 5, 8>), grid, dim3(256), 0,
-                           ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc);
-      else
-        hipLaunchKernelGGL((bsr16_cm_kernel<_Float16, false, 2, 5, 8>), grid, dim3(256), 0,
-                           ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc);
-    } else {
-      const dim3 gc(mb, (n + 255) / 256);
-      const int* ord = nullptr;
-      if (const spmm_status_t st = block_row_order(ctx, mb, gc.y, rowptr, &ord)) {
-        timing_end(ctx, slot);
-        return st;
-      }
-#ifdef SPMM_TUNING
-      static const int env_tt = [] {
-        const char* e = getenv("SPMM_CS16_TT");  // TUNING builds only
-        return e ? atoi(e) : 0;
-      }();
-      const int ntt = env_tt && gc.y > 1 ? (int)gc.y : 0;
-#else
-      constexpr int ntt = 0;
-#endif
-      const dim3 gg = ntt ? dim3((unsigned)(8 * ((mb + 7) / 8) * ntt), 1) : gc;
-#define CS16_LAUNCH(...)                                                                         \
-  do {                                                                                           \
-    if (crow)                                                                                    \
-      hipLaunchKernelGGL((bsr16_f16_cs_kernel<true, 2, 4, 0, 48, __VA_ARGS__>), gg, dim3(64), 0, \
-                         ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C, ldc,   \
-                         ord, masks, ntt);                                                       \
-    else                                                                                         \
-      hipLaunchKernelGGL((bsr16_f16_cs_kernel<false, 2, 4, 0, 48, __VA_ARGS__>), gg, dim3(64),   \
-                         0, ctx->stream, mb, n, rowptr, colind, val, B, ldb, alpha, beta, C,     \
-                         ldc, ord, masks, ntt);                                                  \
-  } while (0)
-      if (msk) CS16_LAUNCH(true, true, 256, true);
-      else if (lv == kBsr16F16Cs) CS16_LAUNCH(true, true);
-      else CS16_LAUNCH(false, true);
-#undef CS16_LAUNCH
-    }
-  } else if (bs == 16 && vec_ok) {
-    const int waves = n <= 64 ? 1 : (n <= 128 ? 2 : 4);
-    dim3 grid(mb, (n + 64 * waves - 1) / (64 * waves));
-    SPMM_BSR_DISPATCH(bsr16_f16_mfma_kernel, SPMM_COMMA kBsr16F16Default, grid, dim3(64 * waves),
-                      ctx->stream, rowd, brow, crow, mb, n, rowptr, colind, val, B, ldb, alpha,
-                      beta, C, ldc);
-  } else {
-    dim3 grid(mb, (n + 63) / 64);
-    hipLaunchKernelGGL(bsr_generic_kernel<_Float16>, grid, dim3(256), 0, ctx->stream, mb, n, bs,
-                       rowd, rowptr, colind, val, B, ldb, brow, alpha, beta, C, ldc, crow);
-  }
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return timed(ctx, [&] {
+    if (bs16_f16_copy_kernels(a, dense_sem))
+      return bs16_f16_copy(a, bs16_f16_analysed(a, dense_sem));
+    if (bs == 16 && fragments_loadable(a.val, a.brow, a.B, ldb, 8)) return fragment_fallback(a);
+    return generic(a);
+  });
 }
 
+// Stages and occupancy hint of the grouped streams: with_grp32_variant / with_grp16_variant.
 spmm_status_t launch_bsrmm_grouped_f32(spmm_context* ctx, int W, int mb, int n, int ngroups,
                                        const int* item_ptr, const int* rows,
                                        const unsigned* wmask, const float* afrag, const float* B,
                                        int ldb, float alpha, float beta, float* C, int ldc) {
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const int slot = timing_begin(ctx);
-  const dim3 grid(ngroups, (n + 127) / 128);
-  // stages and occupancy hint P * 10 + OCC (TUNING builds: SPMM_GRP32_VARIANT); chunks of
-  // 32 block rows per XCD (SPMM_GRP_XM)
-  int gv = 33, xm = 32 / W;
-#ifdef SPMM_TUNING
-  {
-    static const int env = [] {
-      const char* e = getenv("SPMM_GRP32_VARIANT");
-      return e ? atoi(e) : 0;
-    }();
-    static const int env_xm = [] {
-      const char* e = getenv("SPMM_GRP_XM");
-      return e ? atoi(e) : -1;
-    }();
-    switch (env) {
-      case 30: case 32: case 33: case 34: case 42: case 43: case 44: case 52: case 53: case 933:
-        gv = env;
-        break;
-      default:
-        break;
-    }
-    if (env_xm >= 0) xm = env_xm;
-  }
-#endif
-#define GRP32_LAUNCH1(W_, P_, O_)                                                                \
-  hipLaunchKernelGGL((bsr32_f32_grp_kernel<W_, P_, O_>), grid, dim3(64 * W_), 0, ctx->stream,    \
-                     mb, n, item_ptr, rows, wmask, afrag, B, ldb, alpha, beta, C, ldc, xm)
-#ifdef SPMM_TUNING
-#define GRP32_LAUNCH(W_)                                                                         \
-  do {                                                                                           \
-    switch (gv) {                                                                                \
-      case 30: GRP32_LAUNCH1(W_, 3, 0); break;                                                   \
-      case 32: GRP32_LAUNCH1(W_, 3, 2); break;                                                   \
-      case 34: GRP32_LAUNCH1(W_, 3, 4); break;                                                   \
-      case 42: GRP32_LAUNCH1(W_, 4, 2); break;                                                   \
-      case 43: GRP32_LAUNCH1(W_, 4, 3); break;                                                   \
-      case 44: GRP32_LAUNCH1(W_, 4, 4); break;                                                   \
-      case 52: GRP32_LAUNCH1(W_, 5, 2); break;                                                   \
-      case 53: GRP32_LAUNCH1(W_, 5, 3); break;                                                   \
-      case 933:  /* diagnostic: no MFMAs (wrong results) */                                    \
-        hipLaunchKernelGGL((bsr32_f32_grp_kernel<W_, 3, 3, true>), grid, dim3(64 * W_), 0,       \
-                           ctx->stream, mb, n, item_ptr, rows, wmask, afrag, B, ldb, alpha, beta, \
-                           C, ldc, xm);                                                          \
-        break;                                                                                   \
-      default: GRP32_LAUNCH1(W_, 3, 3); break;                                                   \
-    }                                                                                            \
-  } while (0)
-#else
-#define GRP32_LAUNCH(W_) GRP32_LAUNCH1(W_, 3, 3)
-#endif
-  (void)gv;
-  if (W == 4) GRP32_LAUNCH(4);
-  else GRP32_LAUNCH(2);
-#undef GRP32_LAUNCH
-#undef GRP32_LAUNCH1
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return timed(ctx, [&] {
+    const dim3 grid(ngroups, (n + 127) / 128);
+    const int xm = grp_xm(W);
+    with_grp32_variant([&](auto v) {
+      constexpr int V = decltype(v)::value;
+      with_int<4, 2>(W == 4 ? 4 : 2, [&](auto w) {
+        constexpr int W_ = decltype(w)::value;
+        hipLaunchKernelGGL((bsr32_f32_grp_kernel<W_, V / 10 % 10, V % 10, V / 100 == 9>), grid,
+                           dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask, afrag, B,
+                           ldb, alpha, beta, C, ldc, xm);
+      });
+    });
+    return SPMM_STATUS_SUCCESS;
+  });
 }
 
 spmm_status_t launch_bsrmm_grouped_f16(spmm_context* ctx, int W, int mb, int n, int ngroups,
@@ -4657,94 +4620,35 @@ spmm_status_t launch_bsrmm_grouped_f16(spmm_context* ctx, int W, int mb, int n, 
                                        float* C, int ldc, bool crow) {
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
   const _Float16* B = reinterpret_cast<const _Float16*>(B16);
-  const int slot = timing_begin(ctx);
-  const int ntiles = (n + 255) / 256;
-  // stages and occupancy hint: P * 10 + OCC, + 200 for two items per barrier (TUNING builds:
-  // SPMM_GRP_VARIANT; SPMM_GRP_XM groups per XCD chunk)
-  // chunks of 32 block rows per XCD, as the drop-in stream (xcd_block_row): neighbouring
-  // groups share B rows in one L2 (W = 4: 3.10 -> 2.87 ms, profiles/r04e/grp_sweep.jsonl)
-  // tiles together (ntt): a group's column tiles consecutive on one XCD, the later ones
-  // reading the A fragments from L2: products stand-in 2.83 -> 2.62 ms, RCM 6.73 -> 6.38
-  // (profiles/r04n/lines.jsonl)
-  int gv = 33, xm = 32 / W, tt = 1;
-#ifdef SPMM_TUNING
-  {
-    static const int env_tt = [] {
-      const char* e = getenv("SPMM_GRP_TT");
-      return e ? atoi(e) : -1;
-    }();
-    if (env_tt >= 0) tt = env_tt;
-    static const int env = [] {
-      const char* e = getenv("SPMM_GRP_VARIANT");
-      return e ? atoi(e) : 0;
-    }();
-    static const int env_xm = [] {
-      const char* e = getenv("SPMM_GRP_XM");
-      return e ? atoi(e) : -1;
-    }();
-    // (4, 4) with two items per barrier is not offered: at W = 4 the allocator spills the A
-    // fragments in flight (tools/isa_vmcnt.py --inflight). (3, 4) spilled with the vector row
-    // loads (and faulted); with the scalar ones it audits clean
-    // (every TUNING build is audited before it runs: tools/build_tuning.sh)
-    switch (env) {
-      case 30: case 33: case 32: case 42: case 43: case 52: case 53: case 23: case 24:
-      case 243: case 262: case 263: case 1033: case 1043: case 34:
-        gv = env;
-        break;
-      default:
-        break;
-    }
-    if (env_xm >= 0) xm = env_xm;
-  }
-#endif
-  const int ntt = tt && ntiles > 1 ? ntiles : 0;
-  const dim3 grid = ntt ? dim3((unsigned)(8 * ((ngroups + 7) / 8) * ntt), 1)
-                        : dim3((unsigned)ngroups, (unsigned)ntiles);
-#define GRP_LAUNCH2(W_, P_, O_, IPB_, AL_)                                                       \
-  do {                                                                                           \
-    if (crow)                                                                                    \
-      hipLaunchKernelGGL((bsr16_f16_grp_kernel<W_, P_, true, O_, IPB_, AL_>), grid,               \
-                         dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask, afrag, B,   \
-                         ldb, alpha, beta, C, ldc, xm, ngroups, ntt);                            \
-    else                                                                                         \
-      hipLaunchKernelGGL((bsr16_f16_grp_kernel<W_, P_, false, O_, IPB_, AL_>), grid,              \
-                         dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask, afrag, B,   \
-                         ldb, alpha, beta, C, ldc, xm, ngroups, ntt);                            \
-  } while (0)
-#define GRP_LAUNCH1(W_, P_, O_, IPB_) GRP_LAUNCH2(W_, P_, O_, IPB_, false)
-#ifdef SPMM_TUNING
-#define GRP_LAUNCH(W_)                                                                           \
-  do {                                                                                           \
-    switch (gv) {                                                                                \
-      case 30: GRP_LAUNCH1(W_, 3, 0, 1); break;                                                  \
-      case 32: GRP_LAUNCH1(W_, 3, 2, 1); break;                                                  \
-      case 42: GRP_LAUNCH1(W_, 4, 2, 1); break;                                                  \
-      case 43: GRP_LAUNCH1(W_, 4, 3, 1); break;                                                  \
-      case 52: GRP_LAUNCH1(W_, 5, 2, 1); break;                                                  \
-      case 53: GRP_LAUNCH1(W_, 5, 3, 1); break;                                                  \
-      case 23: GRP_LAUNCH1(W_, 2, 3, 1); break;                                                  \
-      case 24: GRP_LAUNCH1(W_, 2, 4, 1); break;                                                  \
-      case 243: GRP_LAUNCH1(W_, 4, 3, 2); break;  /* two items per barrier */                    \
-      case 262: GRP_LAUNCH1(W_, 6, 2, 2); break;                                                 \
-      case 263: GRP_LAUNCH1(W_, 6, 3, 2); break;                                                 \
-      case 34: GRP_LAUNCH1(W_, 3, 4, 1); break;  /* audited again after the scalar row loads */ \
-      case 1033: GRP_LAUNCH2(W_, 3, 3, 1, true); break;  /* fragments through LDS */             \
-      case 1043: GRP_LAUNCH2(W_, 4, 3, 1, true); break;                                          \
-      default: GRP_LAUNCH1(W_, 3, 3, 1); break;                                                  \
-    }                                                                                            \
-  } while (0)
-#else
-#define GRP_LAUNCH(W_) GRP_LAUNCH1(W_, 3, 3, 1)
-#endif
-  (void)gv;
-  if (W == 8) GRP_LAUNCH(8);
-  else if (W == 4) GRP_LAUNCH(4);
-  else GRP_LAUNCH(2);
-#undef GRP_LAUNCH
-#undef GRP_LAUNCH1
-#undef GRP_LAUNCH2
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return timed(ctx, [&] {
+    const int ntiles = (n + 255) / 256;
+    // chunks of 32 block rows per XCD, as the drop-in stream (xcd_block_row): neighbouring
+    // groups share B rows in one L2 (W = 4: 3.10 -> 2.87 ms, profiles/r04e/grp_sweep.jsonl)
+    const int xm = grp_xm(W);
+    // tiles together (ntt): a group's column tiles consecutive on one XCD, the later ones
+    // reading the A fragments from L2: products stand-in 2.83 -> 2.62 ms, RCM 6.73 -> 6.38
+    // (profiles/r04n/lines.jsonl). TUNING builds: SPMM_GRP_TT=0 turns it off
+    const int env_tt = tuning_env_int("SPMM_GRP_TT", -1);
+    const int tt = env_tt >= 0 ? env_tt : 1;
+    const int ntt = tt && ntiles > 1 ? ntiles : 0;
+    const dim3 grid = ntt ? dim3((unsigned)(8 * ((ngroups + 7) / 8) * ntt), 1)
+                          : dim3((unsigned)ngroups, (unsigned)ntiles);
+    with_grp16_variant([&](auto v) {
+      constexpr int V = decltype(v)::value;
+      with_int<8, 4, 2>(W == 8 || W == 4 ? W : 2, [&](auto w) {
+        constexpr int W_ = decltype(w)::value;
+        with_bools(
+            [&](auto cr) {
+              hipLaunchKernelGGL((bsr16_f16_grp_kernel<W_, V / 10 % 10, decltype(cr)::value, V % 10,
+                                                       V / 100 % 10 == 2 ? 2 : 1, V >= 1000>),
+                                 grid, dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask,
+                                 afrag, B, ldb, alpha, beta, C, ldc, xm, ngroups, ntt);
+            },
+            crow);
+      });
+    });
+    return SPMM_STATUS_SUCCESS;
+  });
 }
 
 }  // namespace spmm

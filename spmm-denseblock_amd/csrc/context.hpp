@@ -156,6 +156,10 @@ inline spmm_status_t from_hip(hipError_t e) {
 
 // Kernel launchers (csr_kernels.hip / bsr_kernels.hip). Pointers are device
 // pointers; all shape checks have been done by the API layer.
+// Each launcher picks its kernel at the end of its file: routers of named predicates over
+// the helpers of dispatch.hpp (with_bools / with_int, timed, tuning_env_int). The choice is
+// pinned on the host: bin/dispatch_trace (dispatch_trace.hpp turns launches into text)
+// against tests/golden/dispatch_trace.txt, tests/test_dispatch_trace.py.
 // carry_ws: csrmm_carry_bytes of workspace (split-row partials, rewritten by
 // every launch); the split-row tickets come from ensure_tickets.
 spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* rowptr,

@@ -36,6 +36,10 @@
 #include <climits>
 
 #include "context.hpp"
+#ifdef SPMM_DISPATCH_TRACE
+#include "dispatch_trace.hpp"  // first: dispatch.hpp's launch status goes through it too
+#endif
+#include "dispatch.hpp"
 
 namespace {
 
@@ -1144,101 +1148,106 @@ size_t csrmm_carry_bytes(spmm_context* ctx, int m, int n) {
   return split_array_floats(ctx, n) * sizeof(float) + 256;
 }
 
+namespace {
+
+// What every CSR product launch shares: the merge-path grid (nw waves, one column tile of
+// 64 * vec columns per grid.y), the piece slots of split rows in the workspace (sized by
+// csrmm_carry_bytes for the largest grid) and the handle's tickets (zero between launches).
+struct CsrPlan {
+  int vec, nw;
+  dim3 grid;
+  SplitWs sws;
+  int* tickets;
+};
+spmm_status_t csr_plan(spmm_context* ctx, int m, int n, int vec, int nnz_hint, bool hot,
+                       void* carry_ws, CsrPlan* p) {
+  const int tile = kWave * vec;
+  const int ntiles = (n + tile - 1) / tile;
+  p->vec = vec;
+  p->nw = csr_nwaves(ctx, m, nnz_hint, hot);
+  p->grid = dim3((p->nw + kWavesPerWG - 1) / kWavesPerWG, ntiles);
+  p->sws.slots = static_cast<float*>(carry_ws);
+  p->sws.stride = tile;
+  if (spmm_status_t st = spmm::ensure_tickets(ctx, (size_t)p->nw * ntiles)) return st;
+  p->tickets = ctx->tickets;
+  return SPMM_STATUS_SUCCESS;
+}
+
+// The group kernel (n <= 64, 16-byte rows of B and C): several nonzeros per wave
+// instruction, one column tile. SPMM_CSR_SEQUENTIAL_ROWS keeps the merge-path kernel.
+bool csr_grouped_ok(spmm_context* ctx, int n, const float* B, int ldb, const float* C, int ldc) {
+  return n <= kGroupMaxK && n % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(B) % 16 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
+         (ctx->csr_flags & SPMM_CSR_SEQUENTIAL_ROWS) == 0;
+}
+
+// The merge-path kernel at VEC = p.vec: hot-column hints (fp32 alone; 2: and B below 4 GB)
+// imply nt streams, else nt as the handle's flags say.
+template <typename T>
+void launch_mergepath(spmm_context* ctx, const CsrPlan& p, bool nt, int hot, int m, int n,
+                      const int* rowptr, const int* colind, const T* val, int base, const T* B,
+                      int ldb, float alpha, float beta, float* C, int ldc) {
+  spmm::with_int<4, 2, 1>(p.vec, [&](auto v) {
+    auto go = [&](auto nt_, auto hot_) {
+      hipLaunchKernelGGL((CsrMp<T>::template csr_mergepath_kernel<decltype(v)::value,
+                                                                  decltype(nt_)::value,
+                                                                  decltype(hot_)::value>),
+                         p.grid, dim3(kWG), 0, ctx->stream, m, n, rowptr, colind, val, base, B,
+                         ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
+    };
+    using std::integral_constant;
+    if constexpr (std::is_same_v<T, float>) {
+      if (hot == 2) return go(std::true_type{}, integral_constant<int, 2>{});
+      if (hot) return go(std::true_type{}, integral_constant<int, 1>{});
+    }
+    if (nt) go(std::true_type{}, integral_constant<int, 0>{});
+    else go(std::false_type{}, integral_constant<int, 0>{});
+  });
+}
+
+}  // namespace
+
 spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* rowptr,
                                     const int* colind, const float* val, int base,
                                     const float* B, int ldb, float alpha, float beta, float* C,
                                     int ldc, void* carry_ws, int nnz_hint, int hot) {
   if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const int vec = pick_vec(n, B, ldb, C, ldc);
-  const int tile = kWave * vec;
-  const int ntiles = (n + tile - 1) / tile;
-  const int nw = csr_nwaves(ctx, m, nnz_hint, hot != 0);
-  dim3 grid((nw + kWavesPerWG - 1) / kWavesPerWG, ntiles);
-  dim3 block(kWG);
-  // split rows: piece slots in the workspace (sized by csrmm_carry_bytes for the
-  // largest grid), tickets of the handle (zero between launches)
-  SplitWs sws;
-  sws.slots = static_cast<float*>(carry_ws);
-  sws.stride = tile;
-  if (spmm_status_t st = ensure_tickets(ctx, (size_t)nw * ntiles)) return st;
-  int* tickets = ctx->tickets;
-  const int slot = timing_begin(ctx);
+  CsrPlan p;
+  if (spmm_status_t st =
+          csr_plan(ctx, m, n, pick_vec(n, B, ldb, C, ldc), nnz_hint, hot != 0, carry_ws, &p))
+    return st;
   const bool nt = (ctx->csr_flags & SPMM_CSR_NT_STREAMS) != 0;
-  const bool grouped = n <= kGroupMaxK && n % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 &&
-                      reinterpret_cast<uintptr_t>(B) % 16 == 0 &&
-                      reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
-                      (ctx->csr_flags & SPMM_CSR_SEQUENTIAL_ROWS) == 0;
-  if (grouped) {
-    sws.stride = kWave;  // one column tile: lane l owns column l (n <= 64)
-    dim3 g8((nw + kWavesPerWG - 1) / kWavesPerWG, 1);
-#ifdef SPMM_TUNING
-    static const int pd_env = [] {
-      const char* e = getenv("SPMM_CSR_GROUP_PD");  // TUNING builds only
-      return e ? atoi(e) : 0;
-    }();
-#else
-    constexpr int pd_env = 0;
-#endif
-#define SPMM_LAUNCH_GRP_PD(L, PD)                                                              \
-  if (hot)                                                                                     \
-    hipLaunchKernelGGL((csr_group_kernel<true, L, PD, true>), g8, block, 0, ctx->stream, m, n,  \
-                       rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws, tickets,    \
-                       nw);                                                                     \
-  else if (nt)                                                                                 \
-    hipLaunchKernelGGL((csr_group_kernel<true, L, PD>), g8, block, 0, ctx->stream, m, n,        \
-                       rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws, tickets,    \
-                       nw);                                                                     \
-  else                                                                                         \
-    hipLaunchKernelGGL((csr_group_kernel<false, L, PD>), g8, block, 0, ctx->stream, m, n,       \
-                       rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws, tickets,    \
-                       nw);
+  return timed(ctx, [&] {
+    if (!csr_grouped_ok(ctx, n, B, ldb, C, ldc)) {
+      launch_mergepath(ctx, p, nt, hot, m, n, rowptr, colind, val, base, B, ldb, alpha, beta, C,
+                       ldc);
+      return SPMM_STATUS_SUCCESS;
+    }
+    p.sws.stride = kWave;  // one column tile: lane l owns column l (n <= 64)
+    const dim3 g8(p.grid.x, 1);
     // gathers in flight per wave: 1 at K <= 16, where a gather costs a whole
     // 128-B line and depth is no help; 2 at K = 32 (1.21 vs 1.35 ms on
     // products); 4 at K = 48 / 64 (2.19 / 2.27 ms vs 2.33 / 2.37 for the
-    // main kernel)
+    // main kernel). TUNING builds: SPMM_CSR_GROUP_PD (1 or 4; anything else is 2)
+    const int pd_env = tuning_env_int("SPMM_CSR_GROUP_PD", 0);
     const int pd = pd_env > 0 ? pd_env : (n <= 16 ? 1 : (n <= 32 ? 2 : 4));
-#define SPMM_LAUNCH_GRP(L)                                                                     \
-  if (pd == 1) { SPMM_LAUNCH_GRP_PD(L, 1) }                                                    \
-  else if (pd == 4) { SPMM_LAUNCH_GRP_PD(L, 4) }                                               \
-  else { SPMM_LAUNCH_GRP_PD(L, 2) }
     // lanes per nnz: 4 columns each, so 2 / 4 / 8 / 16 lanes cover K <= 8 / 16 / 32 / 64
-    if (n <= 8) {
-      SPMM_LAUNCH_GRP(2)
-    } else if (n <= 16) {
-      SPMM_LAUNCH_GRP(4)
-    } else if (n <= 32) {
-      SPMM_LAUNCH_GRP(8)
-    } else {
-      SPMM_LAUNCH_GRP(16)
-    }
-#undef SPMM_LAUNCH_GRP
-#undef SPMM_LAUNCH_GRP_PD
-    timing_end(ctx, slot);
-    return from_hip(hipGetLastError());
-  }
-#define SPMM_LAUNCH_MP(V, N)                                                                   \
-  hipLaunchKernelGGL((CsrMp<float>::csr_mergepath_kernel<V, N>), grid, block, 0, ctx->stream,  \
-                     m, n, rowptr, colind, val, base, B, ldb, alpha, beta, C, ldc, sws,        \
-                     tickets, nw)
-#define SPMM_LAUNCH_HOT(V, H)                                                                  \
-  hipLaunchKernelGGL((CsrMp<float>::csr_mergepath_kernel<V, true, H>), grid, block, 0,         \
-                     ctx->stream, m, n, rowptr, colind, val, base, B, ldb, alpha, beta, C,     \
-                     ldc, sws, tickets, nw)
-  if (hot == 2) {
-    if (vec == 4) SPMM_LAUNCH_HOT(4, 2); else if (vec == 2) SPMM_LAUNCH_HOT(2, 2); else SPMM_LAUNCH_HOT(1, 2);
-  } else if (hot) {
-    if (vec == 4) SPMM_LAUNCH_HOT(4, 1); else if (vec == 2) SPMM_LAUNCH_HOT(2, 1); else SPMM_LAUNCH_HOT(1, 1);
-  } else if (vec == 4) {
-    if (nt) SPMM_LAUNCH_MP(4, true); else SPMM_LAUNCH_MP(4, false);
-  } else if (vec == 2) {
-    if (nt) SPMM_LAUNCH_MP(2, true); else SPMM_LAUNCH_MP(2, false);
-  } else {
-    if (nt) SPMM_LAUNCH_MP(1, true); else SPMM_LAUNCH_MP(1, false);
-  }
-#undef SPMM_LAUNCH_MP
-#undef SPMM_LAUNCH_HOT
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+    const int lanes = n <= 8 ? 2 : (n <= 16 ? 4 : (n <= 32 ? 8 : 16));
+    with_int<2, 4, 8, 16>(lanes, [&](auto l) {
+      with_int<1, 4, 2>(pd == 1 || pd == 4 ? pd : 2, [&](auto d) {
+        auto go = [&](auto nt_, auto hot_) {
+          hipLaunchKernelGGL((csr_group_kernel<decltype(nt_)::value, decltype(l)::value,
+                                               decltype(d)::value, decltype(hot_)::value>),
+                             g8, dim3(kWG), 0, ctx->stream, m, n, rowptr, colind, val, base, B,
+                             ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
+        };
+        if (hot) go(std::true_type{}, std::true_type{});  // hot hints imply nt streams
+        else if (nt) go(std::true_type{}, std::false_type{});
+        else go(std::false_type{}, std::false_type{});
+      });
+    });
+    return SPMM_STATUS_SUCCESS;
+  });
 }
 
 // The fp16-input form: always the merge-path kernel (at n <= 64 too, one 64-column tile
@@ -1249,35 +1258,16 @@ spmm_status_t launch_csrmm_rowmajor_f16(spmm_context* ctx, int m, int n, const i
                                         const uint16_t* B, int ldb, float alpha, float beta,
                                         float* C, int ldc, void* carry_ws, int nnz_hint) {
   if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
-  const int vec = pick_vec(n, B, ldb, C, ldc, 2);
-  const int tile = kWave * vec;
-  const int ntiles = (n + tile - 1) / tile;
-  const int nw = csr_nwaves(ctx, m, nnz_hint, false);
-  dim3 grid((nw + kWavesPerWG - 1) / kWavesPerWG, ntiles);
-  dim3 block(kWG);
-  SplitWs sws;
-  sws.slots = static_cast<float*>(carry_ws);
-  sws.stride = tile;
-  if (spmm_status_t st = ensure_tickets(ctx, (size_t)nw * ntiles)) return st;
-  int* tickets = ctx->tickets;
-  const _Float16* val16 = reinterpret_cast<const _Float16*>(val);
-  const _Float16* B16 = reinterpret_cast<const _Float16*>(B);
-  const int slot = timing_begin(ctx);
-  const bool nt = (ctx->csr_flags & SPMM_CSR_NT_STREAMS) != 0;
-#define SPMM_LAUNCH_MP16(V, N)                                                                 \
-  hipLaunchKernelGGL((CsrMp<_Float16>::csr_mergepath_kernel<V, N>), grid, block, 0,            \
-                     ctx->stream, m, n, rowptr, colind, val16, base, B16, ldb, alpha, beta, C, \
-                     ldc, sws, tickets, nw)
-  if (vec == 4) {
-    if (nt) SPMM_LAUNCH_MP16(4, true); else SPMM_LAUNCH_MP16(4, false);
-  } else if (vec == 2) {
-    if (nt) SPMM_LAUNCH_MP16(2, true); else SPMM_LAUNCH_MP16(2, false);
-  } else {
-    if (nt) SPMM_LAUNCH_MP16(1, true); else SPMM_LAUNCH_MP16(1, false);
-  }
-#undef SPMM_LAUNCH_MP16
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  CsrPlan p;
+  if (spmm_status_t st =
+          csr_plan(ctx, m, n, pick_vec(n, B, ldb, C, ldc, 2), nnz_hint, false, carry_ws, &p))
+    return st;
+  return timed(ctx, [&] {
+    launch_mergepath(ctx, p, (ctx->csr_flags & SPMM_CSR_NT_STREAMS) != 0, 0, m, n, rowptr, colind,
+                     reinterpret_cast<const _Float16*>(val), base,
+                     reinterpret_cast<const _Float16*>(B), ldb, alpha, beta, C, ldc);
+    return SPMM_STATUS_SUCCESS;
+  });
 }
 
 // Tile rows beyond grid.y's 65535 go along grid.x (FLAT); past 2^31 - 1 tiles in all
