@@ -160,6 +160,24 @@ spmm_status_t spmm_set_kernel_timing(spmm_handle_t handle, int enable);
  * oldest first, and clears the record. */
 spmm_status_t spmm_get_kernel_times(spmm_handle_t handle, float* ms, int max_count, int* count);
 
+/* Launch record (a test aid: which kernel instantiations a call queued). While
+ * on, every kernel launch made through the handle appends one identifier, in
+ * launch order: the mangled name of a tag type that holds the kernel's own
+ * symbol with its template arguments (csrc/kernel_tag.hpp; tests/kernel_keys.py
+ * maps it onto the .amdhsa_kernel symbol). Host-side only: it records what was
+ * queued, also while the stream is capturing, reads no device memory and does
+ * not synchronise. Like every call on a handle it is for the one host thread
+ * that drives the handle (the list is appended to without a lock; this holds
+ * for the default handle of the handle-less entries too). Off by default,
+ * where a launch costs one test of a flag;
+ * enabling it clears the record, disabling it keeps what was recorded. */
+spmm_status_t spmm_set_launch_record(spmm_handle_t handle, int enable);
+/* Up to max_count identifiers, oldest first; *count = how many were written.
+ * The strings are static: they stay valid for the life of the library. The
+ * record is not cleared (spmm_set_launch_record(handle, 1) does that). */
+spmm_status_t spmm_get_launch_record(spmm_handle_t handle, const char** ids, int max_count,
+                                     int* count);
+
 /* Tuning knob for the CSR merge-path kernel: resident waves per CU the grid
  * is sized for (0 = default). */
 spmm_status_t spmm_set_csr_waves_per_cu(spmm_handle_t handle, int waves_per_cu);

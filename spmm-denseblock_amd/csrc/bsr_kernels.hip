@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 #ifdef SPMM_DISPATCH_TRACE
 #include "dispatch_trace.hpp"  // first: dispatch.hpp's launch status goes through it too
 #endif
@@ -3998,8 +3999,8 @@ spmm_status_t cs2_segments(spmm_context* ctx, int mb, int nnzb, int ntiles, cons
   int4* sg = reinterpret_cast<int4*>(ctx->order);
   int4* sp = sg + seg_cap;
   const int split_if = (int)std::min<long>(0x7fffffff, 2 * ((long)nnzb + slots - 1) / slots);
-  hipLaunchKernelGGL(seg_build_kernel, dim3(1), dim3(1024), 0, ctx->stream, mb, rowptr, L, split_if,
-                     seg_cap, split_cap, (int)parts_cap, sg, sp);
+  SPMM_LAUNCH(ctx, seg_build_kernel, dim3(1), dim3(1024), 0, mb, rowptr, L, split_if,
+              seg_cap, split_cap, (int)parts_cap, sg, sp);
   *segs = sg;
   *splits = sp;
   *part = reinterpret_cast<float*>(ctx->scratch);
@@ -4016,8 +4017,8 @@ spmm_status_t block_row_order(spmm_context* ctx, int mb, int ntiles, const int* 
   if (force == 2 || (force != 1 && force != 3 && waves > kLptRounds * slots))
     return SPMM_STATUS_SUCCESS;
   if (spmm_status_t st = spmm::ensure_order_buffer(ctx, mb)) return st;
-  hipLaunchKernelGGL(block_row_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, mb, rowptr,
-                     crp, m, sub, ctx->order);
+  SPMM_LAUNCH(ctx, block_row_order_kernel, dim3(1), dim3(1024), 0, mb, rowptr,
+              crp, m, sub, ctx->order);
   *order = ctx->order;
   return SPMM_STATUS_SUCCESS;
 }
@@ -4124,8 +4125,8 @@ spmm_status_t panel_probe(spmm_context* ctx, long long nblocks, int sub, const f
   if (hipError_t e = hipMemsetAsync(*pstat, 0, 2 * sizeof(**pstat), ctx->stream))
     return spmm::from_hip(e);
   const int ns = (int)std::min<long long>(nblocks, kPanelSamples);
-  hipLaunchKernelGGL(panel_probe_kernel, dim3((ns + 4 * kPanelPerWave - 1) / (4 * kPanelPerWave)),
-                     dim3(256), 0, ctx->stream, nblocks, ns, sub, val, *pstat);
+  SPMM_LAUNCH(ctx, panel_probe_kernel, dim3((ns + 4 * kPanelPerWave - 1) / (4 * kPanelPerWave)),
+              dim3(256), 0, nblocks, ns, sub, val, *pstat);
   return SPMM_STATUS_SUCCESS;
 }
 
@@ -4136,9 +4137,9 @@ void launch_panel(const BsrArgs<float>& a, dim3 grid, int mbx, const int* ord,
   spmm::with_bools(
       [&](auto cr, auto c64) {
         constexpr bool CR = decltype(cr)::value, C64 = decltype(c64)::value;
-        hipLaunchKernelGGL(
+        SPMM_LAUNCH(a.ctx, 
             (bsr32_f32_panel_kernel<CR, C64, C64 ? SPMM_PANEL_D64 : SPMM_PANEL_D128, SUB>), grid,
-            dim3(64), 0, a.ctx->stream, mbx, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb, a.alpha,
+            dim3(64), 0, mbx, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb, a.alpha,
             a.beta, a.C, a.ldc, ord, pstat);
       },
       a.crow, a.n <= 64);
@@ -4153,10 +4154,10 @@ spmm_status_t bs32_dense_lds(const BsrArgs<float>& a, bool split) {
   spmm::with_bools(
       [&](auto cr, auto sp) {
         constexpr bool CR = decltype(cr)::value, SP = decltype(sp)::value;
-        hipLaunchKernelGGL((bsr32_f32_lds_kernel<CR, 2, 32, false, 24, SP, SP && CR>), grid,
-                           dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
-                           a.ldb, a.alpha, a.beta, a.C, a.ldc, nullptr, nullptr, nullptr, 0,
-                           nullptr);
+        SPMM_LAUNCH(a.ctx, (bsr32_f32_lds_kernel<CR, 2, 32, false, 24, SP, SP && CR>), grid,
+                    dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
+                    a.ldb, a.alpha, a.beta, a.C, a.ldc, nullptr, nullptr, nullptr, 0,
+                    nullptr);
       },
       a.crow, split);
   return SPMM_STATUS_SUCCESS;
@@ -4195,9 +4196,9 @@ spmm_status_t bs32_column_stream(const BsrArgs<float>& a, bool msk, int lv) {
         [&](auto cr, auto o32, auto c64_) {
           constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
                          C64 = decltype(c64_)::value;
-          hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, true, false, C64>),
-                             g2, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val,
-                             a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt, a.masks);
+          SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, true, false, C64>),
+                      g2, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind, a.val,
+                      a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt, a.masks);
         },
         a.crow, narrow, c64);
   } else {
@@ -4206,11 +4207,11 @@ spmm_status_t bs32_column_stream(const BsrArgs<float>& a, bool msk, int lv) {
       spmm::with_bools(
           [&](auto cr, auto c64_) {
             constexpr bool CR = decltype(cr)::value, C64 = decltype(c64_)::value;
-            hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, decltype(o32)::value, true,
-                                                     decltype(ant)::value, false, false, C64>),
-                               g2, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind,
-                               a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt,
-                               a.masks, pstat);
+            SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, decltype(o32)::value, true,
+                                              decltype(ant)::value, false, false, C64>),
+                        g2, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind,
+                        a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt,
+                        a.masks, pstat);
           },
           a.crow, c64);
     };
@@ -4220,8 +4221,8 @@ spmm_status_t bs32_column_stream(const BsrArgs<float>& a, bool msk, int lv) {
   }
   if (pstat) launch_panel<false>(a, g2, a.mb, ord, pstat);
   if (spl)
-    hipLaunchKernelGGL(seg_fixup_kernel, dim3(nspl, ntiles), dim3(256), 0, ctx->stream, a.n, spl,
-                       pt, a.alpha, a.beta, a.C, a.ldc);
+    SPMM_LAUNCH(ctx, seg_fixup_kernel, dim3(nspl, ntiles), dim3(256), 0, a.n, spl,
+                pt, a.alpha, a.beta, a.C, a.ldc);
   return SPMM_STATUS_SUCCESS;
 }
 
@@ -4253,10 +4254,10 @@ spmm_status_t bs64_sub_stream(const BsrArgs<float>& a) {
       [&](auto cr, auto o32, auto c64) {  // c64: the 64-column tile
         constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
                        C64 = decltype(c64)::value;
-        hipLaunchKernelGGL((bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, false, true, C64>),
-                           g2, dim3(64), 0, ctx->stream, mb2, a.n, a.rowptr, a.colind, a.val, a.B,
-                           a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, nullptr, nullptr, nullptr,
-                           pstat);
+        SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, false, true, C64>),
+                    g2, dim3(64), 0, mb2, a.n, a.rowptr, a.colind, a.val, a.B,
+                    a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, nullptr, nullptr, nullptr,
+                    pstat);
       },
       a.crow, narrow, a.n <= 64);
   if (pstat) launch_panel<true>(a, g2, mb2, ord, pstat);
@@ -4275,17 +4276,17 @@ spmm_status_t fragment_fallback(const BsrArgs<T>& a) {
         constexpr bool RD = decltype(rd)::value, BR = decltype(br)::value,
                        CR = decltype(cr)::value;
         if constexpr (std::is_same_v<T, _Float16>)
-          hipLaunchKernelGGL((bsr16_f16_mfma_kernel<RD, BR, CR, kBsr16F16Default>), grid, block, 0,
-                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
-                             a.alpha, a.beta, a.C, a.ldc);
+          SPMM_LAUNCH(a.ctx, (bsr16_f16_mfma_kernel<RD, BR, CR, kBsr16F16Default>), grid, block, 0,
+                      a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                      a.alpha, a.beta, a.C, a.ldc);
         else if (a.bs == 32)
-          hipLaunchKernelGGL((bsr32_f32_mfma_kernel<RD, BR, CR, kBsr32Default>), grid, block, 0,
-                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
-                             a.alpha, a.beta, a.C, a.ldc);
+          SPMM_LAUNCH(a.ctx, (bsr32_f32_mfma_kernel<RD, BR, CR, kBsr32Default>), grid, block, 0,
+                      a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                      a.alpha, a.beta, a.C, a.ldc);
         else
-          hipLaunchKernelGGL((bsr16_f32_mfma_kernel<RD, BR, CR, kBsr16Default>), grid, block, 0,
-                             a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
-                             a.alpha, a.beta, a.C, a.ldc);
+          SPMM_LAUNCH(a.ctx, (bsr16_f32_mfma_kernel<RD, BR, CR, kBsr16Default>), grid, block, 0,
+                      a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+                      a.alpha, a.beta, a.C, a.ldc);
       },
       a.rowd, a.brow, a.crow);
   return SPMM_STATUS_SUCCESS;
@@ -4300,9 +4301,9 @@ spmm_status_t bs16_column_masked(const BsrArgs<float>& a) {
   spmm::with_int<64, 128, 256>(cols, [&](auto co) {
     spmm::with_bools(
         [&](auto cr) {
-          hipLaunchKernelGGL(
+          SPMM_LAUNCH(a.ctx, 
               (bsr16_cm_kernel<float, decltype(cr)::value, 2, 5, 1, decltype(co)::value>), grid,
-              dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
+              dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
               a.alpha, a.beta, a.C, a.ldc);
         },
         a.crow);
@@ -4318,10 +4319,10 @@ void launch_small(const BsrArgs<float>& a, bool v2, Tail... tail) {
   spmm::with_int<2, 4, 8>(a.bs, [&](auto bs) {
     spmm::with_bools(
         [&](auto v2_, auto rd, auto cr) {
-          hipLaunchKernelGGL((bsr_small_kernel<decltype(bs)::value, decltype(v2_)::value ? 2 : 1,
-                                               decltype(rd)::value, decltype(cr)::value>),
-                             grid, dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind,
-                             a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, tail...);
+          SPMM_LAUNCH(a.ctx, (bsr_small_kernel<decltype(bs)::value, decltype(v2_)::value ? 2 : 1,
+                                        decltype(rd)::value, decltype(cr)::value>),
+                      grid, dim3(256), 0, a.mb, a.n, a.rowptr, a.colind,
+                      a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, tail...);
         },
         v2, a.rowd, a.crow);
   });
@@ -4358,8 +4359,8 @@ spmm_status_t small_grouped(const BsrArgs<float>& a) {
     const double mean = (double)a.nnzb / nch;
     int gshift = 0;
     while ((4.0 * mean) / (1 << gshift) > 1023.0) ++gshift;
-    hipLaunchKernelGGL(block_row_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, nch,
-                       a.rowptr, nullptr, a.mb, 0, ctx->order, 32 / bs * cx, gshift);
+    SPMM_LAUNCH(ctx, block_row_order_kernel, dim3(1), dim3(1024), 0, nch,
+                a.rowptr, nullptr, a.mb, 0, ctx->order, 32 / bs * cx, gshift);
     ord = ctx->order;
     lgrid.x = nch * cx;
   }
@@ -4370,14 +4371,14 @@ spmm_status_t small_grouped(const BsrArgs<float>& a) {
   const dim3 pgrid(std::min(ngroups, 1024));
   spmm::with_int<2, 4, 8>(bs, [&](auto bs_) {
     constexpr int BS = decltype(bs_)::value;
-    hipLaunchKernelGGL(small_grp_probe_kernel<BS>, pgrid, dim3(64), 0, ctx->stream, a.mb, ngroups,
-                       a.rowptr, a.colind, stat);
+    SPMM_LAUNCH(ctx, small_grp_probe_kernel<BS>, pgrid, dim3(64), 0, a.mb, ngroups,
+                a.rowptr, a.colind, stat);
     spmm::with_bools(
         [&](auto rd, auto cr) {
-          hipLaunchKernelGGL((bsr_small_grp_kernel<BS, decltype(rd)::value, decltype(cr)::value>),
-                             lgrid, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind,
-                             a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc,
-                             SPMM_SGRP_LPT != 2 && ord ? 1 : xm, dirty, ord, a.nnzb, stat);
+          SPMM_LAUNCH(ctx, (bsr_small_grp_kernel<BS, decltype(rd)::value, decltype(cr)::value>),
+                      lgrid, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind,
+                      a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc,
+                      SPMM_SGRP_LPT != 2 && ord ? 1 : xm, dirty, ord, a.nnzb, stat);
         },
         a.rowd, a.crow);
   });
@@ -4400,9 +4401,9 @@ spmm_status_t small_valu(const BsrArgs<float>& a) {
 template <typename T>
 spmm_status_t generic(const BsrArgs<T>& a) {
   const dim3 grid(a.mb, (a.n + 63) / 64);
-  hipLaunchKernelGGL(bsr_generic_kernel<T>, grid, dim3(256), 0, a.ctx->stream, a.mb, a.n, a.bs,
-                     a.rowd, a.rowptr, a.colind, a.val, a.B, a.ldb, a.brow, a.alpha, a.beta, a.C,
-                     a.ldc, a.crow);
+  SPMM_LAUNCH(a.ctx, bsr_generic_kernel<T>, grid, dim3(256), 0, a.mb, a.n, a.bs,
+              a.rowd, a.rowptr, a.colind, a.val, a.B, a.ldb, a.brow, a.alpha, a.beta, a.C,
+              a.ldc, a.crow);
   return SPMM_STATUS_SUCCESS;
 }
 
@@ -4412,9 +4413,9 @@ spmm_status_t bs16_f16_column_masked(const BsrArgs<_Float16>& a) {
   const dim3 grid(a.mb, (a.n + 255) / 256);
   spmm::with_bools(
       [&](auto cr) {
-        hipLaunchKernelGGL((bsr16_cm_kernel<_Float16, decltype(cr)::value, 2, 5, 8>), grid,
-                           dim3(256), 0, a.ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
-                           a.ldb, a.alpha, a.beta, a.C, a.ldc);
+        SPMM_LAUNCH(a.ctx, (bsr16_cm_kernel<_Float16, decltype(cr)::value, 2, 5, 8>), grid,
+                    dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
+                    a.ldb, a.alpha, a.beta, a.C, a.ldc);
       },
       a.crow);
   return SPMM_STATUS_SUCCESS;
@@ -4432,11 +4433,11 @@ spmm_status_t bs16_f16_column_stream(const BsrArgs<_Float16>& a, bool msk, int l
   auto stream = [&](auto ant, auto mk) {
     spmm::with_bools(
         [&](auto cr) {
-          hipLaunchKernelGGL((bsr16_f16_cs_kernel<decltype(cr)::value, 2, 4, 0, 48,
-                                                  decltype(ant)::value, true, 256,
-                                                  decltype(mk)::value>),
-                             gg, dim3(64), 0, ctx->stream, a.mb, a.n, a.rowptr, a.colind, a.val,
-                             a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, a.masks, ntt);
+          SPMM_LAUNCH(ctx, (bsr16_f16_cs_kernel<decltype(cr)::value, 2, 4, 0, 48,
+                                           decltype(ant)::value, true, 256,
+                                           decltype(mk)::value>),
+                      gg, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind, a.val,
+                      a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, a.masks, ntt);
         },
         a.crow);
   };
@@ -4495,8 +4496,8 @@ namespace spmm {
 spmm_status_t launch_bsr32_analysis(spmm_context* ctx, spmm_direction_t dir, int nnzb,
                                     const float* val, unsigned* masks, float* val_col) {
   if (nnzb == 0) return SPMM_STATUS_SUCCESS;
-  hipLaunchKernelGGL(bsr32_analysis_kernel, dim3((nnzb + 3) / 4), dim3(256), 0, ctx->stream, nnzb,
-                     dir == SPMM_DIRECTION_ROW ? 1 : 0, val, masks, val_col);
+  SPMM_LAUNCH(ctx, bsr32_analysis_kernel, dim3((nnzb + 3) / 4), dim3(256), 0, nnzb,
+              dir == SPMM_DIRECTION_ROW ? 1 : 0, val, masks, val_col);
   return from_hip(hipGetLastError());
 }
 
@@ -4504,9 +4505,9 @@ spmm_status_t launch_bsr16_analysis(spmm_context* ctx, spmm_direction_t dir, int
                                     const uint16_t* val, unsigned* masks, uint16_t* val_col) {
   if (nnzb == 0) return SPMM_STATUS_SUCCESS;
   const long long per_block = 4 * kAna16Bpw;  // 4 waves, kAna16Bpw blocks each
-  hipLaunchKernelGGL(bsr16_analysis_kernel, dim3((unsigned)((nnzb + per_block - 1) / per_block)),
-                     dim3(256), 0, ctx->stream, nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0, val,
-                     masks, val_col);
+  SPMM_LAUNCH(ctx, bsr16_analysis_kernel, dim3((unsigned)((nnzb + per_block - 1) / per_block)),
+              dim3(256), 0, nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0, val,
+              masks, val_col);
   return from_hip(hipGetLastError());
 }
 
@@ -4561,9 +4562,9 @@ spmm_status_t launch_hybrid32_fused(spmm_context* ctx, int m, int n, float alpha
     with_bools(
         [&](auto sp) {
           constexpr bool SP = decltype(sp)::value;
-          hipLaunchKernelGGL((bsr32_f32_lds_kernel<true, 2, 32, true, 24, SP, SP>), grid, dim3(256),
-                             0, ctx->stream, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc,
-                             crp, cci, cv, m, ord);
+          SPMM_LAUNCH(ctx, (bsr32_f32_lds_kernel<true, 2, 32, true, 24, SP, SP>), grid, dim3(256),
+                      0, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc,
+                      crp, cci, cv, m, ord);
         },
         (ctx->hybrid_flags & SPMM_HYBRID_SPLIT_BF16) != 0);
     return SPMM_STATUS_SUCCESS;
@@ -4604,9 +4605,9 @@ spmm_status_t launch_bsrmm_grouped_f32(spmm_context* ctx, int W, int mb, int n, 
       constexpr int V = decltype(v)::value;
       with_int<4, 2>(W == 4 ? 4 : 2, [&](auto w) {
         constexpr int W_ = decltype(w)::value;
-        hipLaunchKernelGGL((bsr32_f32_grp_kernel<W_, V / 10 % 10, V % 10, V / 100 == 9>), grid,
-                           dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask, afrag, B,
-                           ldb, alpha, beta, C, ldc, xm);
+        SPMM_LAUNCH(ctx, (bsr32_f32_grp_kernel<W_, V / 10 % 10, V % 10, V / 100 == 9>), grid,
+                    dim3(64 * W_), 0, mb, n, item_ptr, rows, wmask, afrag, B,
+                    ldb, alpha, beta, C, ldc, xm);
       });
     });
     return SPMM_STATUS_SUCCESS;
@@ -4639,10 +4640,10 @@ spmm_status_t launch_bsrmm_grouped_f16(spmm_context* ctx, int W, int mb, int n, 
         constexpr int W_ = decltype(w)::value;
         with_bools(
             [&](auto cr) {
-              hipLaunchKernelGGL((bsr16_f16_grp_kernel<W_, V / 10 % 10, decltype(cr)::value, V % 10,
-                                                       V / 100 % 10 == 2 ? 2 : 1, V >= 1000>),
-                                 grid, dim3(64 * W_), 0, ctx->stream, mb, n, item_ptr, rows, wmask,
-                                 afrag, B, ldb, alpha, beta, C, ldc, xm, ngroups, ntt);
+              SPMM_LAUNCH(ctx, (bsr16_f16_grp_kernel<W_, V / 10 % 10, decltype(cr)::value, V % 10,
+                                                V / 100 % 10 == 2 ? 2 : 1, V >= 1000>),
+                          grid, dim3(64 * W_), 0, mb, n, item_ptr, rows, wmask,
+                          afrag, B, ldb, alpha, beta, C, ldc, xm, ngroups, ntt);
             },
             crow);
       });

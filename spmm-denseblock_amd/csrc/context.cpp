@@ -309,6 +309,23 @@ spmm_status_t spmm_get_kernel_times(spmm_handle_t h, float* ms, int max_count, i
   return SPMM_STATUS_SUCCESS;
 }
 
+spmm_status_t spmm_set_launch_record(spmm_handle_t h, int enable) {
+  if (!h) return SPMM_STATUS_NOT_INITIALIZED;
+  h->record = enable != 0;
+  if (enable) h->launches.clear();
+  return SPMM_STATUS_SUCCESS;
+}
+
+spmm_status_t spmm_get_launch_record(spmm_handle_t h, const char** ids, int max_count,
+                                     int* count) {
+  if (!h) return SPMM_STATUS_NOT_INITIALIZED;
+  if (!count || (max_count > 0 && !ids)) return SPMM_STATUS_INVALID_VALUE;
+  int c = 0;
+  for (size_t s = 0; s < h->launches.size() && c < max_count; ++s) ids[c++] = h->launches[s];
+  *count = c;
+  return SPMM_STATUS_SUCCESS;
+}
+
 spmm_status_t spmm_set_csr_waves_per_cu(spmm_handle_t h, int w) {
   if (!h) return SPMM_STATUS_NOT_INITIALIZED;
   if (w < 0 || w > 32) return SPMM_STATUS_INVALID_VALUE;

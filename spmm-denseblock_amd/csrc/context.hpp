@@ -104,6 +104,11 @@ struct spmm_context {
   std::vector<hipEvent_t> ev_start, ev_stop;
   size_t ev_used = 0;
 
+  // Launch record (spmm_set_launch_record): while on, every kernel launch through this
+  // handle appends its identifier (launch_record.hpp), a static string, in launch order.
+  bool record = false;
+  std::vector<const char*> launches;
+
   std::mutex mu;  // serialises workspace growth for the shared default handle
 };
 

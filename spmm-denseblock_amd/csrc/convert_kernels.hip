@@ -22,6 +22,7 @@
 #include <climits>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 
 namespace {
 
@@ -298,7 +299,7 @@ namespace spmm {
 
 spmm_status_t launch_scan_counts(spmm_context* ctx, const int* count, int n, int* out,
                                  long long* total, int base) {
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, count, n, base, out, total);
+  SPMM_LAUNCH(ctx, scan_kernel, dim3(1), dim3(1024), 0, count, n, base, out, total);
   return from_hip(hipGetLastError());
 }
 
@@ -313,8 +314,8 @@ spmm_status_t spmm_xcoo2csr(spmm_handle_t handle, const int* cooRowInd, int nnz,
     return SPMM_STATUS_INVALID_VALUE;
   if (!csrRowPtr || (nnz > 0 && !cooRowInd)) return SPMM_STATUS_INVALID_VALUE;
   spmm_context* ctx = handle;
-  hipLaunchKernelGGL(coo2csr_kernel, dim3((m + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                     cooRowInd, nnz, m, (int)idxBase, csrRowPtr);
+  SPMM_LAUNCH(ctx, coo2csr_kernel, dim3((m + 1 + 255) / 256), dim3(256), 0,
+              cooRowInd, nnz, m, (int)idxBase, csrRowPtr);
   return spmm::from_hip(hipGetLastError());
 }
 
@@ -339,11 +340,11 @@ spmm_status_t spmm_xcsr2bsr_nnz_dev(spmm_handle_t handle, spmm_direction_t dir, 
   int* count = reinterpret_cast<int*>(ws + 32);
   if (hipMemsetAsync(ws, 0, 32, ctx->stream) != hipSuccess) return SPMM_STATUS_EXECUTION_FAILED;
   if (mb > 0)
-    hipLaunchKernelGGL((csr2bsr_kernel<false, true>), dim3((mb + 3) / 4), dim3(kWG), 0,
-                       ctx->stream, m, n, mb, blockDim, csrRowPtr, csrColInd, nullptr,
-                       (int)descrA->base, count, nullptr, 0, nullptr, nullptr, bad);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, count, mb,
-                     (int)descrC->base, bsrRowPtr, total);
+    SPMM_LAUNCH(ctx, (csr2bsr_kernel<false, true>), dim3((mb + 3) / 4), dim3(kWG), 0, m, n, mb,
+                blockDim, csrRowPtr, csrColInd, nullptr,
+                (int)descrA->base, count, nullptr, 0, nullptr, nullptr, bad);
+  SPMM_LAUNCH(ctx, scan_kernel, dim3(1), dim3(1024), 0, count, mb,
+              (int)descrC->base, bsrRowPtr, total);
   long long host[2] = {0, 0};
   if (hipMemcpyAsync(host, ws, 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -385,13 +386,13 @@ spmm_status_t spmm_scsr2bsr_dev(spmm_handle_t handle, spmm_direction_t dir, int 
     return SPMM_STATUS_EXECUTION_FAILED;
   const dim3 grid((mb + 3) / 4);
   if (dir == SPMM_DIRECTION_ROW)
-    hipLaunchKernelGGL((csr2bsr_kernel<true, true>), grid, dim3(kWG), 0, ctx->stream, m, n, mb,
-                       blockDim, csrRowPtr, csrColInd, csrVal, (int)descrA->base, nullptr,
-                       bsrRowPtr, (int)descrC->base, bsrColInd, bsrVal, bad);
+    SPMM_LAUNCH(ctx, (csr2bsr_kernel<true, true>), grid, dim3(kWG), 0, m, n, mb,
+                blockDim, csrRowPtr, csrColInd, csrVal, (int)descrA->base, nullptr,
+                bsrRowPtr, (int)descrC->base, bsrColInd, bsrVal, bad);
   else
-    hipLaunchKernelGGL((csr2bsr_kernel<true, false>), grid, dim3(kWG), 0, ctx->stream, m, n, mb,
-                       blockDim, csrRowPtr, csrColInd, csrVal, (int)descrA->base, nullptr,
-                       bsrRowPtr, (int)descrC->base, bsrColInd, bsrVal, bad);
+    SPMM_LAUNCH(ctx, (csr2bsr_kernel<true, false>), grid, dim3(kWG), 0, m, n, mb,
+                blockDim, csrRowPtr, csrColInd, csrVal, (int)descrA->base, nullptr,
+                bsrRowPtr, (int)descrC->base, bsrColInd, bsrVal, bad);
   return spmm::from_hip(hipGetLastError());
 }
 
@@ -409,13 +410,13 @@ spmm_status_t spmm_sbsr2csr_dev(spmm_handle_t handle, spmm_direction_t dir, int 
   if (mb == 0) return SPMM_STATUS_SUCCESS;
   const dim3 grid((mb + 3) / 4);
   if (dir == SPMM_DIRECTION_ROW)
-    hipLaunchKernelGGL((bsr2csr_kernel<true>), grid, dim3(kWG), 0, ctx->stream, mb, blockDim,
-                       bsrRowPtr, bsrColInd, bsrVal, (int)descrA->base, (int)descrC->base,
-                       csrRowPtr, csrColInd, csrVal);
+    SPMM_LAUNCH(ctx, (bsr2csr_kernel<true>), grid, dim3(kWG), 0, mb, blockDim,
+                bsrRowPtr, bsrColInd, bsrVal, (int)descrA->base, (int)descrC->base,
+                csrRowPtr, csrColInd, csrVal);
   else
-    hipLaunchKernelGGL((bsr2csr_kernel<false>), grid, dim3(kWG), 0, ctx->stream, mb, blockDim,
-                       bsrRowPtr, bsrColInd, bsrVal, (int)descrA->base, (int)descrC->base,
-                       csrRowPtr, csrColInd, csrVal);
+    SPMM_LAUNCH(ctx, (bsr2csr_kernel<false>), grid, dim3(kWG), 0, mb, blockDim,
+                bsrRowPtr, bsrColInd, bsrVal, (int)descrA->base, (int)descrC->base,
+                csrRowPtr, csrColInd, csrVal);
   return spmm::from_hip(hipGetLastError());
 }
 
@@ -442,11 +443,11 @@ spmm_status_t spmm_xbsr_reblock32_nnzb(spmm_handle_t handle, spmm_direction_t di
   int* count = reinterpret_cast<int*>(ws + 32);
   if (hipMemsetAsync(ws, 0, 32, ctx->stream) != hipSuccess) return SPMM_STATUS_EXECUTION_FAILED;
   if (mb32 > 0)
-    hipLaunchKernelGGL(reblock32_kernel<false>, dim3((mb32 + 3) / 4), dim3(kWG), 0, ctx->stream,
-                       mb, R, shift, bsrRowPtr, bsrColInd, count, nullptr, nullptr, nullptr,
-                       nullptr, blockDim, dir == SPMM_DIRECTION_ROW ? 1 : 0, bad);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, count, mb32, 0,
-                     bsrRowPtr32, total);
+    SPMM_LAUNCH(ctx, reblock32_kernel<false>, dim3((mb32 + 3) / 4), dim3(kWG), 0,
+                mb, R, shift, bsrRowPtr, bsrColInd, count, nullptr, nullptr, nullptr,
+                nullptr, blockDim, dir == SPMM_DIRECTION_ROW ? 1 : 0, bad);
+  SPMM_LAUNCH(ctx, scan_kernel, dim3(1), dim3(1024), 0, count, mb32, 0,
+              bsrRowPtr32, total);
   long long host[2] = {0, 0};
   if (hipMemcpyAsync(host, ws, 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -482,13 +483,13 @@ spmm_status_t spmm_sbsr_reblock32(spmm_handle_t handle, spmm_direction_t dir, in
   int* bad = reinterpret_cast<int*>(ws);
   int* map_k = reinterpret_cast<int*>(ws + 32);
   int* map_off = map_k + nnzb;
-  hipLaunchKernelGGL(reblock32_kernel<true>, dim3((mb32 + 3) / 4), dim3(kWG), 0, ctx->stream, mb,
-                     R, shift, bsrRowPtr, bsrColInd, nullptr, bsrRowPtr32, bsrColInd32, map_k,
-                     map_off, blockDim, dir == SPMM_DIRECTION_ROW ? 1 : 0, bad);
+  SPMM_LAUNCH(ctx, reblock32_kernel<true>, dim3((mb32 + 3) / 4), dim3(kWG), 0, mb,
+              R, shift, bsrRowPtr, bsrColInd, nullptr, bsrRowPtr32, bsrColInd32, map_k,
+              map_off, blockDim, dir == SPMM_DIRECTION_ROW ? 1 : 0, bad);
   const long long total = (long long)nnzb * blockDim * blockDim;
   const long long blocks = std::min<long long>((total + 255) / 256, 65536);
-  hipLaunchKernelGGL(reblock32_values_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
-                     total, blockDim, blockDim * blockDim, bsrVal, map_k, map_off, bsrVal32);
+  SPMM_LAUNCH(ctx, reblock32_values_kernel, dim3((unsigned)blocks), dim3(256), 0,
+              total, blockDim, blockDim * blockDim, bsrVal, map_k, map_off, bsrVal32);
   return spmm::from_hip(hipGetLastError());
 }
 

@@ -36,6 +36,7 @@
 #include <climits>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 #ifdef SPMM_DISPATCH_TRACE
 #include "dispatch_trace.hpp"  // first: dispatch.hpp's launch status goes through it too
 #endif
@@ -1117,13 +1118,13 @@ spmm_status_t launch_csr_hot_analysis(spmm_context* ctx, int k, long long nnz, c
   hipError_t e = hipMemsetAsync(cnt, 0, cnt_bytes + kHotBins * 4, ctx->stream);
   if (e != hipSuccess) return from_hip(e);
   const int grid = ctx->num_cus * 8;
-  hipLaunchKernelGGL(col_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, nnz, colind, base, k,
-                     cnt);
-  hipLaunchKernelGGL(count_hist_kernel, dim3(ctx->num_cus), dim3(256), 0, ctx->stream, k, cnt,
-                     hist);
-  hipLaunchKernelGGL(hot_select_kernel, dim3(1), dim3(1024), 0, ctx->stream, hist, hot_rows, thr);
-  hipLaunchKernelGGL(hot_tag_kernel, dim3(grid), dim3(256), 0, ctx->stream, nnz, colind, base, k,
-                     cnt, thr, colind_out);
+  SPMM_LAUNCH(ctx, col_count_kernel, dim3(grid), dim3(256), 0, nnz, colind, base, k,
+              cnt);
+  SPMM_LAUNCH(ctx, count_hist_kernel, dim3(ctx->num_cus), dim3(256), 0, k, cnt,
+              hist);
+  SPMM_LAUNCH(ctx, hot_select_kernel, dim3(1), dim3(1024), 0, hist, hot_rows, thr);
+  SPMM_LAUNCH(ctx, hot_tag_kernel, dim3(grid), dim3(256), 0, nnz, colind, base, k,
+              cnt, thr, colind_out);
   return from_hip(hipGetLastError());
 }
 
@@ -1189,11 +1190,11 @@ void launch_mergepath(spmm_context* ctx, const CsrPlan& p, bool nt, int hot, int
                       int ldb, float alpha, float beta, float* C, int ldc) {
   spmm::with_int<4, 2, 1>(p.vec, [&](auto v) {
     auto go = [&](auto nt_, auto hot_) {
-      hipLaunchKernelGGL((CsrMp<T>::template csr_mergepath_kernel<decltype(v)::value,
-                                                                  decltype(nt_)::value,
-                                                                  decltype(hot_)::value>),
-                         p.grid, dim3(kWG), 0, ctx->stream, m, n, rowptr, colind, val, base, B,
-                         ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
+      SPMM_LAUNCH(ctx, (CsrMp<T>::template csr_mergepath_kernel<decltype(v)::value,
+                                                           decltype(nt_)::value,
+                                                           decltype(hot_)::value>),
+                  p.grid, dim3(kWG), 0, m, n, rowptr, colind, val, base, B,
+                  ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
     };
     using std::integral_constant;
     if constexpr (std::is_same_v<T, float>) {
@@ -1236,10 +1237,10 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
     with_int<2, 4, 8, 16>(lanes, [&](auto l) {
       with_int<1, 4, 2>(pd == 1 || pd == 4 ? pd : 2, [&](auto d) {
         auto go = [&](auto nt_, auto hot_) {
-          hipLaunchKernelGGL((csr_group_kernel<decltype(nt_)::value, decltype(l)::value,
-                                               decltype(d)::value, decltype(hot_)::value>),
-                             g8, dim3(kWG), 0, ctx->stream, m, n, rowptr, colind, val, base, B,
-                             ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
+          SPMM_LAUNCH(ctx, (csr_group_kernel<decltype(nt_)::value, decltype(l)::value,
+                                        decltype(d)::value, decltype(hot_)::value>),
+                      g8, dim3(kWG), 0, m, n, rowptr, colind, val, base, B,
+                      ldb, alpha, beta, C, ldc, p.sws, p.tickets, p.nw);
         };
         if (hot) go(std::true_type{}, std::true_type{});  // hot hints imply nt streams
         else if (nt) go(std::true_type{}, std::false_type{});
@@ -1277,13 +1278,13 @@ spmm_status_t launch_transpose(spmm_context* ctx, int rows, int cols, const floa
   if (rows == 0 || cols == 0) return SPMM_STATUS_SUCCESS;
   const unsigned tx = (cols + 63) / 64, ty = (rows + 63) / 64;
   if (ty <= 65535) {
-    hipLaunchKernelGGL(transpose4_kernel<false>, dim3(tx, ty), dim3(256), 0, ctx->stream, rows,
-                       cols, src, ld_src, dst, ld_dst, beta, tx);
+    SPMM_LAUNCH(ctx, transpose4_kernel<false>, dim3(tx, ty), dim3(256), 0, rows,
+                cols, src, ld_src, dst, ld_dst, beta, tx);
     return from_hip(hipGetLastError());
   }
   if ((unsigned long long)tx * ty > 0x7fffffffull) return SPMM_STATUS_NOT_SUPPORTED;
-  hipLaunchKernelGGL(transpose4_kernel<true>, dim3(tx * ty), dim3(256), 0, ctx->stream, rows,
-                     cols, src, ld_src, dst, ld_dst, beta, tx);
+  SPMM_LAUNCH(ctx, transpose4_kernel<true>, dim3(tx * ty), dim3(256), 0, rows,
+              cols, src, ld_src, dst, ld_dst, beta, tx);
   return from_hip(hipGetLastError());
 }
 
@@ -1294,13 +1295,13 @@ spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const ui
   if (rows == 0 || cols == 0) return SPMM_STATUS_SUCCESS;
   const unsigned tx = (cols + 63) / 64, ty = (rows + 63) / 64;
   if (ty <= 65535) {
-    hipLaunchKernelGGL(transpose16x4_kernel<false>, dim3(tx, ty), dim3(256), 0, ctx->stream, rows,
-                       cols, src, ld_src, dst, ld_dst, tx);
+    SPMM_LAUNCH(ctx, transpose16x4_kernel<false>, dim3(tx, ty), dim3(256), 0, rows,
+                cols, src, ld_src, dst, ld_dst, tx);
     return from_hip(hipGetLastError());
   }
   if ((unsigned long long)tx * ty > 0x7fffffffull) return SPMM_STATUS_NOT_SUPPORTED;
-  hipLaunchKernelGGL(transpose16x4_kernel<true>, dim3(tx * ty), dim3(256), 0, ctx->stream, rows,
-                     cols, src, ld_src, dst, ld_dst, tx);
+  SPMM_LAUNCH(ctx, transpose16x4_kernel<true>, dim3(tx * ty), dim3(256), 0, rows,
+              cols, src, ld_src, dst, ld_dst, tx);
   return from_hip(hipGetLastError());
 }
 

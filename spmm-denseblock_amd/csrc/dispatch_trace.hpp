@@ -22,10 +22,9 @@
 #include <typeinfo>
 #include <utility>
 
-namespace spmm_trace {
+#include "kernel_tag.hpp"
 
-template <auto K>
-struct KTag {};
+namespace spmm_trace {
 
 // One finished line (no newline). Defined by the program that links the traced objects.
 void emit(const std::string& line);

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 
 namespace {
 
@@ -81,8 +82,8 @@ spmm_status_t launch_csrmm_f64(spmm_context* ctx, int m, int n, const int* rowpt
                                bool crow) {
   if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
   const int slot = timing_begin(ctx);
-  hipLaunchKernelGGL(csr_f64_kernel, dim3((m + 3) / 4, (n + 63) / 64), dim3(256), 0, ctx->stream,
-                     m, n, rowptr, colind, val, base, B, ldb, brow, alpha, beta, C, ldc, crow);
+  SPMM_LAUNCH(ctx, csr_f64_kernel, dim3((m + 3) / 4, (n + 63) / 64), dim3(256), 0,
+              m, n, rowptr, colind, val, base, B, ldb, brow, alpha, beta, C, ldc, crow);
   timing_end(ctx, slot);
   return from_hip(hipGetLastError());
 }
@@ -93,9 +94,9 @@ spmm_status_t launch_bsrmm_f64(spmm_context* ctx, spmm_direction_t dir, int mb, 
                                double* C, int ldc, bool crow) {
   if (mb == 0 || n == 0) return SPMM_STATUS_SUCCESS;
   const int slot = timing_begin(ctx);
-  hipLaunchKernelGGL(bsr_f64_kernel, dim3(mb, (n + 63) / 64), dim3(256), 0, ctx->stream, mb, n, bs,
-                     dir == SPMM_DIRECTION_ROW, rowptr, colind, val, B, ldb, brow, alpha, beta, C,
-                     ldc, crow);
+  SPMM_LAUNCH(ctx, bsr_f64_kernel, dim3(mb, (n + 63) / 64), dim3(256), 0, mb, n, bs,
+              dir == SPMM_DIRECTION_ROW, rowptr, colind, val, B, ldb, brow, alpha, beta, C,
+              ldc, crow);
   timing_end(ctx, slot);
   return from_hip(hipGetLastError());
 }

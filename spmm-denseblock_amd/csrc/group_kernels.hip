@@ -30,6 +30,7 @@
 #include <cstdint>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 
 namespace {
 
@@ -614,11 +615,11 @@ spmm_status_t launch_grp_build(spmm_context* ctx, int W, int BS, bool pass2, int
 #define GRP_BUILD(W_, BS_)                                                                     \
   do {                                                                                         \
     if (pass2)                                                                                 \
-      hipLaunchKernelGGL((grp_build_kernel<W_, BS_, true>), grid, dim3(64), 0, ctx->stream, mb, \
-                         nnzb, ngroups, rp, ci, mk, cnt, maxj, item_ptr, rows, src);            \
+      SPMM_LAUNCH(ctx, (grp_build_kernel<W_, BS_, true>), grid, dim3(64), 0, mb, \
+                  nnzb, ngroups, rp, ci, mk, cnt, maxj, item_ptr, rows, src);            \
     else                                                                                       \
-      hipLaunchKernelGGL((grp_build_kernel<W_, BS_, false>), grid, dim3(64), 0, ctx->stream,   \
-                         mb, nnzb, ngroups, rp, ci, mk, cnt, maxj, item_ptr, rows, src);        \
+      SPMM_LAUNCH(ctx, (grp_build_kernel<W_, BS_, false>), grid, dim3(64), 0,   \
+                  mb, nnzb, ngroups, rp, ci, mk, cnt, maxj, item_ptr, rows, src);        \
   } while (0)
   if (BS == 16) {
     if (W == 8) GRP_BUILD(8, 16);
@@ -638,9 +639,9 @@ spmm_status_t launch_grp_wmask(spmm_context* ctx, long long nitems, int W, int E
   if (nwork == 0) return SPMM_STATUS_SUCCESS;
   const dim3 grid((unsigned)((nwork + 255) / 256));
   if (E == 16)
-    hipLaunchKernelGGL(grp_wmask_kernel<16>, grid, dim3(256), 0, ctx->stream, nwork, W, src, wmask);
+    SPMM_LAUNCH(ctx, grp_wmask_kernel<16>, grid, dim3(256), 0, nwork, W, src, wmask);
   else
-    hipLaunchKernelGGL(grp_wmask_kernel<8>, grid, dim3(256), 0, ctx->stream, nwork, W, src, wmask);
+    SPMM_LAUNCH(ctx, grp_wmask_kernel<8>, grid, dim3(256), 0, nwork, W, src, wmask);
   return from_hip(hipGetLastError());
 }
 
@@ -649,8 +650,8 @@ spmm_status_t launch_bsr16_grp_fill(spmm_context* ctx, long long nitems, int W, 
                                     unsigned* afrag) {
   if (nitems == 0) return SPMM_STATUS_SUCCESS;
   const long long units = (nitems + kFill16Items - 1) / kFill16Items * W;
-  hipLaunchKernelGGL(bsr16_grp_fill_kernel, dim3((unsigned)units), dim3(64), 0, ctx->stream, nitems,
-                     W, dir == SPMM_DIRECTION_ROW ? 1 : 0, rows, src, val, afrag);
+  SPMM_LAUNCH(ctx, bsr16_grp_fill_kernel, dim3((unsigned)units), dim3(64), 0, nitems,
+              W, dir == SPMM_DIRECTION_ROW ? 1 : 0, rows, src, val, afrag);
   return from_hip(hipGetLastError());
 }
 
@@ -659,17 +660,17 @@ spmm_status_t launch_bsr32_grp_fill(spmm_context* ctx, long long nitems, int W, 
                                     float* afrag) {
   if (nitems == 0) return SPMM_STATUS_SUCCESS;
   const long long units = (nitems + kFill32Items - 1) / kFill32Items * W;
-  hipLaunchKernelGGL(bsr32_grp_fill_kernel, dim3((unsigned)units), dim3(64), 0, ctx->stream, nitems,
-                     W, dir == SPMM_DIRECTION_ROW ? 1 : 0, rows, src, val, afrag);
+  SPMM_LAUNCH(ctx, bsr32_grp_fill_kernel, dim3((unsigned)units), dim3(64), 0, nitems,
+              W, dir == SPMM_DIRECTION_ROW ? 1 : 0, rows, src, val, afrag);
   return from_hip(hipGetLastError());
 }
 
 spmm_status_t launch_grp_mask32(spmm_context* ctx, spmm_direction_t dir, int nnzb, const float* val,
                                 unsigned* masks, float* cols) {
   if (nnzb == 0) return SPMM_STATUS_SUCCESS;
-  hipLaunchKernelGGL(grp_mask32_kernel, dim3((unsigned)(((long long)nnzb + 3) / 4)), dim3(256), 0,
-                     ctx->stream, (long long)nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0, val, masks,
-                     dir == SPMM_DIRECTION_ROW ? cols : nullptr);
+  SPMM_LAUNCH(ctx, grp_mask32_kernel, dim3((unsigned)(((long long)nnzb + 3) / 4)), dim3(256), 0,
+              (long long)nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0, val, masks,
+              dir == SPMM_DIRECTION_ROW ? cols : nullptr);
   return from_hip(hipGetLastError());
 }
 
@@ -678,8 +679,8 @@ spmm_status_t launch_bsr32_grp_fillc(spmm_context* ctx, long long nitems, int W,
                                      float* afrag) {
   if (nitems == 0) return SPMM_STATUS_SUCCESS;
   const long long units = (nitems + kFill32Items - 1) / kFill32Items * W;
-  hipLaunchKernelGGL(bsr32_grp_fillc_kernel, dim3((unsigned)units), dim3(64), 0, ctx->stream, nitems,
-                     W, rows, src, cols, masks, afrag);
+  SPMM_LAUNCH(ctx, bsr32_grp_fillc_kernel, dim3((unsigned)units), dim3(64), 0, nitems,
+              W, rows, src, cols, masks, afrag);
   return from_hip(hipGetLastError());
 }
 
@@ -687,14 +688,14 @@ spmm_status_t launch_grp_mask16(spmm_context* ctx, spmm_direction_t dir, int nnz
                                 const uint16_t* val, unsigned* masks) {
   if (nnzb == 0) return SPMM_STATUS_SUCCESS;
   const long long per_block = 4 * 2 * kMask16Pairs;  // 4 waves, kMask16Pairs block pairs each
-  hipLaunchKernelGGL(grp_mask16_kernel, dim3((unsigned)((nnzb + per_block - 1) / per_block)),
-                     dim3(256), 0, ctx->stream, (long long)nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0,
-                     val, masks);
+  SPMM_LAUNCH(ctx, grp_mask16_kernel, dim3((unsigned)((nnzb + per_block - 1) / per_block)),
+              dim3(256), 0, (long long)nnzb, dir == SPMM_DIRECTION_ROW ? 1 : 0,
+              val, masks);
   return from_hip(hipGetLastError());
 }
 
 spmm_status_t launch_grp_stats(spmm_context* ctx, const int* maxj, int n, int* stats) {
-  hipLaunchKernelGGL(grp_stats_kernel, dim3(1), dim3(1024), 0, ctx->stream, maxj, n, stats);
+  SPMM_LAUNCH(ctx, grp_stats_kernel, dim3(1), dim3(1024), 0, maxj, n, stats);
   return from_hip(hipGetLastError());
 }
 

@@ -30,6 +30,7 @@
 #include <cstdint>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 
 namespace {
 
@@ -257,11 +258,23 @@ inline int group_lanes(int n) {
 
 using Kernel = void (*)(int, int, int, const int*, const int*, int, const float*, long long,
                         const float*, long long, float, float, float*);
+// a kernel chosen at run time, with its launch-record identifier (launch_record.hpp)
+struct Picked {
+  Kernel fn;
+  const char* id;
+};
+template <auto K>
+Picked picked() {
+  return {K, spmm::launch_id<K>()};
+}
 
 template <int G, int NC>
-Kernel pick(bool vec, bool full) {
-  if (vec) return full ? sddmm_kernel<G, NC, true, true> : sddmm_kernel<G, NC, true, false>;
-  return full ? sddmm_kernel<G, NC, false, true> : sddmm_kernel<G, NC, false, false>;
+Picked pick(bool vec, bool full) {
+  if (vec)
+    return full ? picked<sddmm_kernel<G, NC, true, true>>()
+                : picked<sddmm_kernel<G, NC, true, false>>();
+  return full ? picked<sddmm_kernel<G, NC, false, true>>()
+              : picked<sddmm_kernel<G, NC, false, false>>();
 }
 
 }  // namespace
@@ -280,13 +293,14 @@ spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* 
   if (n == 0) {
     const unsigned zgrid = (unsigned)std::min<long long>(((long long)nnz + kWG - 1) / kWG, 65536);
     const int zslot = timing_begin(ctx);
-    hipLaunchKernelGGL(sddmm_zero_kernel, dim3(zgrid), dim3(kWG), 0, ctx->stream, m, nnz, rowptr,
-                       base, alpha, beta, out);
+    SPMM_LAUNCH(ctx, sddmm_zero_kernel, dim3(zgrid), dim3(kWG), 0, m, nnz, rowptr,
+                base, alpha, beta, out);
     timing_end(ctx, zslot);
     return from_hip(hipGetLastError());
   }
-  Kernel kern = nullptr;
-  if (NC > kMaxChunks) kern = vec ? sddmm_wide_kernel<true> : sddmm_wide_kernel<false>;
+  Picked kern{};
+  if (NC > kMaxChunks)
+    kern = vec ? picked<sddmm_wide_kernel<true>>() : picked<sddmm_wide_kernel<false>>();
   else if (G == 1) kern = pick<1, 1>(vec, full);
   else if (G == 2) kern = pick<2, 1>(vec, full);
   else if (G == 4) kern = pick<4, 1>(vec, full);
@@ -305,8 +319,9 @@ spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* 
                                               (long long)ctx->num_cus * 128);
   const unsigned grid = (unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG);
   const int slot = timing_begin(ctx);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kWG), 0, ctx->stream, m, n, nnz, rowptr, colind, base,
-                     X, (long long)ldx, Y, (long long)ldy, alpha, beta, out);
+  spmm::note_launch(ctx, kern.id);
+  hipLaunchKernelGGL(kern.fn, dim3(grid), dim3(kWG), 0, ctx->stream, m, n, nnz, rowptr, colind,
+                     base, X, (long long)ldx, Y, (long long)ldy, alpha, beta, out);
   timing_end(ctx, slot);
   return from_hip(hipGetLastError());
 }

@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "context.hpp"
+#include "launch_record.hpp"
 
 namespace {
 
@@ -321,10 +322,10 @@ inline void scan_counts(spmm_context* ctx, const int* count, int len, int* out, 
     return;
   }
   const int nb = scan_chunks((size_t)len);
-  hipLaunchKernelGGL(chunk_sum_kernel, dim3(nb), dim3(kWG), 0, ctx->stream, count, len, sums);
+  SPMM_LAUNCH(ctx, chunk_sum_kernel, dim3(nb), dim3(kWG), 0, count, len, sums);
   (void)spmm::launch_scan_counts(ctx, sums, nb, offs, total, 0);
-  hipLaunchKernelGGL(chunk_scan_kernel, dim3(nb), dim3(kWG), 0, ctx->stream, count, len, offs,
-                     base, out);
+  SPMM_LAUNCH(ctx, chunk_scan_kernel, dim3(nb), dim3(kWG), 0, count, len, offs,
+              base, out);
 }
 
 }  // namespace
@@ -352,8 +353,8 @@ spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
     return SPMM_STATUS_NOT_SUPPORTED;
   const int baseA = (int)descrA->base, baseC = (int)descrC->base;
   if (nnz == 0) {
-    hipLaunchKernelGGL(fill_int_kernel, dim3(grid_for((long long)n + 1)), dim3(kWG), 0,
-                       ctx->stream, cscColPtr, (long long)n + 1, baseC);
+    SPMM_LAUNCH(ctx, fill_int_kernel, dim3(grid_for((long long)n + 1)), dim3(kWG), 0, cscColPtr,
+                (long long)n + 1, baseC);
     return spmm::from_hip(hipGetLastError());
   }
   const int passes = radix_passes(n);
@@ -388,8 +389,8 @@ spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
   if (hipMemsetAsync(ws, 0, off_count + sizeof(int) * (size_t)n, ctx->stream) != hipSuccess)
     return SPMM_STATUS_EXECUTION_FAILED;
   timed(ctx, [&] {
-    hipLaunchKernelGGL(col_count_kernel, dim3(grid_for(std::max<long long>(nnz, m))), dim3(kWG),
-                       0, ctx->stream, m, n, nnz, csrRowPtr, csrColInd, baseA, count, bad);
+    SPMM_LAUNCH(ctx, col_count_kernel, dim3(grid_for(std::max<long long>(nnz, m))), dim3(kWG),
+                0, m, n, nnz, csrRowPtr, csrColInd, baseA, count, bad);
   });
   timed(ctx, [&] { scan_counts(ctx, count, n, cscColPtr, total, baseC, sums, offs); });
   long long host[2] = {0, 0};
@@ -408,18 +409,18 @@ spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
     int* pay_out = last && perm ? perm : pbuf[j & 1];
     timed(ctx, [&] {
       if (first)
-        hipLaunchKernelGGL(digit_count_kernel<true>, dim3(ntiles), dim3(kSortWG), 0, ctx->stream,
-                           nnz, ntiles, shift, keys_in, csrRowPtr, baseA, tile_count);
+        SPMM_LAUNCH(ctx, digit_count_kernel<true>, dim3(ntiles), dim3(kSortWG), 0,
+                    nnz, ntiles, shift, keys_in, csrRowPtr, baseA, tile_count);
       else
-        hipLaunchKernelGGL(digit_count_kernel<false>, dim3(ntiles), dim3(kSortWG), 0, ctx->stream,
-                           nnz, ntiles, shift, keys_in, csrRowPtr, baseA, tile_count);
+        SPMM_LAUNCH(ctx, digit_count_kernel<false>, dim3(ntiles), dim3(kSortWG), 0,
+                    nnz, ntiles, shift, keys_in, csrRowPtr, baseA, tile_count);
     });
     timed(ctx, [&] { scan_counts(ctx, tile_count, (int)ncount, prefix, total, 0, sums, offs); });
     timed(ctx, [&] {
 #define SPMM_SCATTER(F, L)                                                                    \
-  hipLaunchKernelGGL((digit_scatter_kernel<F, L>), dim3(ntiles), dim3(kSortWG), 0, ctx->stream, \
-                     nnz, ntiles, shift, keys_in, pay_in, csrRowPtr, baseA, prefix, keys_out,   \
-                     pay_out)
+  SPMM_LAUNCH(ctx, (digit_scatter_kernel<F, L>), dim3(ntiles), dim3(kSortWG), 0, \
+              nnz, ntiles, shift, keys_in, pay_in, csrRowPtr, baseA, prefix, keys_out,   \
+              pay_out)
       if (first && last) SPMM_SCATTER(true, true);
       else if (first) SPMM_SCATTER(true, false);
       else if (last) SPMM_SCATTER(false, true);
@@ -432,14 +433,14 @@ spmm_status_t spmm_csr2csc_dev(spmm_handle_t handle, int m, int n, int nnz,
   }
   int* rows = reinterpret_cast<int*>(ws + off_buf + buf_bytes * (size_t)(nkeys + npay));
   timed(ctx, [&] {
-    hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_for((long long)m * 8)), dim3(kWG), 0,
-                       ctx->stream, m, nnz, csrRowPtr, rows);
+    SPMM_LAUNCH(ctx, expand_rows_kernel, dim3(grid_for((long long)m * 8)), dim3(kWG), 0, m, nnz,
+                csrRowPtr, rows);
   });
   timed(ctx, [&] {
     const dim3 grid(grid_for(nnz));
 #define SPMM_GATHER(VB)                                                                      \
-  hipLaunchKernelGGL(csc_gather_kernel<VB>, grid, dim3(kWG), 0, ctx->stream, nnz, csrRowPtr, \
-                     baseA, baseC, sorted, rows, csrVal, cscRowInd, cscVal, perm)
+  SPMM_LAUNCH(ctx, csc_gather_kernel<VB>, grid, dim3(kWG), 0, nnz, csrRowPtr, \
+              baseA, baseC, sorted, rows, csrVal, cscRowInd, cscVal, perm)
     if (valueBytes == 0) SPMM_GATHER(0);
     else if (valueBytes == 2) SPMM_GATHER(2);
     else if (valueBytes == 4) SPMM_GATHER(4);

@@ -15,6 +15,14 @@
 // the fp32 BSR entry). The hash (FNV-1a, 64 bits) is over every line of every call in call
 // order, so the sequence within each call is pinned too, not only the set of lines.
 //
+// With the argument "cases" the program instead reads one launcher call per line of
+// standard input and answers each with one line: the tags of the kernels that call
+// launches, in order (tests/test_kernel_cases.py asks it which kernels the cases of
+// tests/kernel_cases.py reach). The lines, all fields integers:
+//   bsr f16 bs n rowd brow crow voff boff coff ldb ldc mb kb nnzb masks dense bsr_flags hybrid_flags
+//   csr f16 m n boff coff ldb ldc nnz hot csr_flags
+//   hybrid m n ldb ldc hybrid_flags
+//
 // The argument grids are subsets of the full product (which runs to millions of calls):
 // the arguments that pick a kernel family (bs, direction, orders, n) are crossed in full,
 // and every other argument is varied one at a time (a few in pairs) from a set of base
@@ -22,7 +30,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -36,6 +47,8 @@ extern const char spmm_trace_no_fatbin[64] = {};
 }
 
 namespace {
+bool g_cases;                     // "cases" mode: emit() keeps the launches' tags only
+std::vector<std::string> g_tags;
 std::vector<std::string> g_order;
 std::map<std::string, long> g_count;
 uint64_t g_hash;
@@ -76,6 +89,10 @@ void* grow(void** p, size_t* have, size_t need) {
 
 namespace spmm_trace {
 void emit(const std::string& line) {
+  if (g_cases) {
+    if (line[0] != '=') g_tags.push_back(line.substr(0, line.find(' ')));
+    return;
+  }
   for (unsigned char c : line) g_hash = (g_hash ^ c) * 1099511628211ull;
   g_hash = (g_hash ^ '\n') * 1099511628211ull;
   if (g_count[line]++ == 0) g_order.push_back(line);
@@ -144,7 +161,7 @@ struct BsrCase {
   int bsr_flags = 0, hybrid_flags = 0;
 };
 
-void run_bsr(const BsrCase& c, bool f16) {
+void run_bsr(const BsrCase& c, bool f16, int ldb_abs = 0, int ldc_abs = 0) {
   g_ctx->bsr_flags = c.bsr_flags;
   g_ctx->hybrid_flags = c.hybrid_flags;
   g_ctx->small_path = -1;
@@ -154,8 +171,8 @@ void run_bsr(const BsrCase& c, bool f16) {
   const auto oc = c.crow ? SPMM_ORDER_ROW : SPMM_ORDER_COL;
   // a column-major operand's leading dimension counts rows
   const int rows_b = (c.kb ? c.kb : c.mb) * c.bs, rows_c = c.mb * c.bs;
-  const int ldb = c.wide ? kWideLdb : (c.brow ? c.n : rows_b) + c.ldb_add;
-  const int ldc = (c.crow ? c.n : rows_c) + c.ldc_add;
+  const int ldb = ldb_abs ? ldb_abs : c.wide ? kWideLdb : (c.brow ? c.n : rows_b) + c.ldb_add;
+  const int ldc = ldc_abs ? ldc_abs : (c.crow ? c.n : rows_c) + c.ldc_add;
   const int kb = c.kb ? c.kb : c.mb;
   float* C = fake<float>(4, c.coff);
   const unsigned* masks = c.masks ? kMasks : nullptr;
@@ -387,12 +404,67 @@ void transpose_grid() {
   section_end("launch_transpose16");
 }
 
+// "cases" mode: one launcher call per input line, its launches' tags per output line
+int run_cases() {
+  g_cases = true;
+  std::string line;
+  while (std::getline(std::cin, line)) {
+    std::istringstream in(line);
+    std::string kind;
+    in >> kind;
+    std::vector<long long> f;
+    for (long long x; in >> x;) f.push_back(x);
+    g_tags.clear();
+    g_ctx->csr_flags = SPMM_CSR_NT_STREAMS;
+    g_ctx->hybrid_flags = 0;
+    if (kind == "bsr" && f.size() == 18) {
+      BsrCase c;
+      c.bs = f[1], c.n = f[2], c.rowd = f[3], c.brow = f[4], c.crow = f[5];
+      c.voff = f[6], c.boff = f[7], c.coff = f[8];
+      c.mb = f[11], c.kb = f[12], c.nnzb = f[13], c.masks = f[14], c.dense = f[15];
+      c.bsr_flags = f[16], c.hybrid_flags = f[17];
+      run_bsr(c, f[0] != 0, (int)f[9], (int)f[10]);
+    } else if (kind == "csr" && f.size() == 10) {
+      g_ctx->csr_flags = (int)f[9];
+      void* ws = fake<void>(9);
+      if (f[0])
+        spmm::launch_csrmm_rowmajor_f16(g_ctx, f[1], f[2], kRowptr, kColind,
+                                        fake<const uint16_t>(2), 0,
+                                        fake<const uint16_t>(3, f[3]), f[5], 1.f, 0.f,
+                                        fake<float>(4, f[4]), f[6], ws, f[7]);
+      else
+        spmm::launch_csrmm_rowmajor(g_ctx, f[1], f[2], kRowptr, kColind, fake<const float>(2), 0,
+                                    fake<const float>(3, f[3]), f[5], 1.f, 0.f,
+                                    fake<float>(4, f[4]), f[6], ws, f[7], (int)f[8]);
+    } else if (kind == "hybrid" && f.size() == 5) {
+      g_ctx->hybrid_flags = (int)f[4];
+      spmm::launch_hybrid32_fused(g_ctx, f[0], f[1], 1.f, kRowptr, kColind, fake<const float>(2),
+                                  fake<const int>(6), fake<const int>(7), fake<const float>(8),
+                                  fake<const float>(3), f[2], 0.f, fake<float>(4), f[3]);
+    } else {
+      std::fprintf(stderr, "dispatch_trace cases: bad line: %s\n", line.c_str());
+      return 2;
+    }
+    std::string out;
+    for (const std::string& t : g_tags) out += (out.empty() ? "" : " ") + t;
+    std::printf("%s\n", out.c_str());
+  }
+  return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
   spmm_context ctx;
   ctx.num_cus = 256;
   g_ctx = &ctx;
+  if (argc > 1 && !std::strcmp(argv[1], "cases")) {
+    const int rc = run_cases();
+    std::free(ctx.scratch);
+    std::free(ctx.order);
+    std::free(ctx.tickets);
+    return rc;
+  }
 
   section_begin();
   bsr_grid(false);

@@ -53,6 +53,51 @@ def check(status: int, where: str) -> None:
         raise SpmmError(status, where)
 
 
+def kernel_key(symbol: str) -> str:
+    """A kernel's mangled symbol up to the end of its nested name: namespace, kernel name
+    and template arguments. The parameter list after it is left out: its substitutions
+    (S2_ ...) are numbered differently once the symbol sits inside a tag's own template
+    argument (csrc/kernel_tag.hpp), as in a launch-record identifier or a dispatch trace."""
+    assert symbol.startswith("_ZN"), symbol
+    i, depth = 3, 0
+    while True:
+        c = symbol[i]
+        if c.isdigit():  # <length><identifier>
+            j = i
+            while symbol[j].isdigit():
+                j += 1
+            i = j + int(symbol[i:j])
+        elif c == "I":
+            depth, i = depth + 1, i + 1
+        elif c == "L":  # a literal: L<type><value>E
+            i = symbol.index("E", i) + 1
+        elif symbol.startswith("DF", i):  # _Float16 (DF16_)
+            i = symbol.index("_", i) + 1
+        elif c == "E":
+            i += 1
+            if depth == 0:
+                return symbol[:i]
+            depth -= 1
+        else:  # a one-letter builtin type
+            i += 1
+
+
+def launch_key(ident: str) -> str:
+    """The key of a kernel, from its `.amdhsa_kernel` symbol, a launch-record identifier
+    (spmm_get_launch_record) or a dispatch-trace tag (both hold the symbol inside the tag
+    type's mangled name): kernel_key of the symbol plus the leading parameters of builtin
+    type, which are spelled the same in all three (no substitution has occurred yet).
+    They tell apart two kernels of one name in different files (col_count_kernel of
+    csr_kernels.hip and of transpose_kernels.hip), so the key is unique per shipped kernel
+    (tests/test_kernel_cases.py)."""
+    sym = ident[ident.index("_ZN"):]
+    key = kernel_key(sym)
+    i = len(key)
+    while i < len(sym) and sym[i] in "abcdefghijlmnostvwxyPKRV":
+        i += 1
+    return sym[:i]
+
+
 _P = c_void_p
 _PI = POINTER(c_int)
 # name -> (restype, argtypes)
@@ -69,6 +114,8 @@ _PROTOS = {
     "spmm_set_mat_index_base": (c_int, [_P, c_int]),
     "spmm_set_kernel_timing": (c_int, [_P, c_int]),
     "spmm_get_kernel_times": (c_int, [_P, POINTER(c_float), c_int, _PI]),
+    "spmm_set_launch_record": (c_int, [_P, c_int]),
+    "spmm_get_launch_record": (c_int, [_P, POINTER(c_char_p), c_int, _PI]),
     "spmm_set_csr_waves_per_cu": (c_int, [_P, c_int]),
     "spmm_csr_default_waves_per_cu": (c_int, [c_int, c_int]),
     "spmm_set_csr_options": (c_int, [_P, c_int]),

@@ -15,11 +15,12 @@ through the C ABI. The functions mirror the reference's operator interfaces:
 """
 from __future__ import annotations
 
-from ctypes import byref, c_float, c_int, c_void_p
+import contextlib
+from ctypes import byref, c_char_p, c_float, c_int, c_void_p
 
 import torch
 
-from ._lib import (DIRECTION_ROW, ORDER_COL, ORDER_ROW, SpmmError, check, lib)
+from ._lib import (DIRECTION_ROW, ORDER_COL, ORDER_ROW, SpmmError, check, launch_key, lib)
 
 
 def _ptr(t: torch.Tensor | None) -> c_void_p:
@@ -68,6 +69,29 @@ class Handle:
         check(lib().spmm_get_kernel_times(self._h, buf, max_count, byref(cnt)),
               "spmm_get_kernel_times")
         return list(buf[: cnt.value])
+
+    @contextlib.contextmanager
+    def launch_record(self):
+        """spmm_set_launch_record / spmm_get_launch_record around a block: yields a list
+        that holds, once the block has ended, the key (``_lib.launch_key``: the mangled
+        name with its template arguments) of every kernel the handle launched in it, in
+        order. Host-side: it records what was queued and synchronises nothing."""
+        keys: list[str] = []
+        check(lib().spmm_set_launch_record(self._h, 1), "spmm_set_launch_record")
+        try:
+            yield keys
+        finally:
+            cnt = c_int(0)
+            cap = 1 << 12
+            while True:
+                buf = (c_char_p * cap)()
+                check(lib().spmm_get_launch_record(self._h, buf, cap, byref(cnt)),
+                      "spmm_get_launch_record")
+                if cnt.value < cap:
+                    break
+                cap *= 4
+            check(lib().spmm_set_launch_record(self._h, 0), "spmm_set_launch_record")
+            keys.extend(launch_key(buf[i].decode()) for i in range(cnt.value))
 
     def set_csr_waves_per_cu(self, w: int) -> None:
         check(lib().spmm_set_csr_waves_per_cu(self._h, w), "spmm_set_csr_waves_per_cu")

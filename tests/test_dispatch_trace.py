@@ -21,31 +21,14 @@ import subprocess
 
 import pytest
 
+from kernel_keys import UNREACHABLE, kernel_key
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "spmm-denseblock_amd")
 EXE = os.path.join(PKG, "bin", "dispatch_trace")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "dispatch_trace.txt")
 ASM = [os.path.join(PKG, "build", f"{k}-hip-amdgcn-amd-amdhsa-gfx950.s")
        for k in ("csr_kernels", "bsr_kernels")]
-
-# Kernels that ship but that no argument tuple of a release build reaches: (pattern over
-# the kernel's name and template arguments, how many it names, the condition that keeps
-# them out). Findings for a later change; nothing is dropped from the check silently.
-UNREACHABLE = [
-    # csr_group_kernel<NT, L, PD, HOT>: the launcher instantiates PD 1 / 2 / 4 at every L,
-    # for a TUNING build's SPMM_CSR_GROUP_PD; a release build derives both from n
-    # (n <= 16: L 2 / 4 with PD 1; n <= 32: L 8 with PD 2; else L 16 with PD 4)
-    (r"16csr_group_kernelILb[01]ELi[24]ELi[24]ELb[01]EE", 12, "L 2 / 4 with PD 2 / 4"),
-    (r"16csr_group_kernelILb[01]ELi8ELi[14]ELb[01]EE", 6, "L 8 with PD 1 / 4"),
-    (r"16csr_group_kernelILb[01]ELi16ELi[12]ELb[01]EE", 6, "L 16 with PD 1 / 2"),
-    # the column streams without nt A copies: SPMM_BSR_VARIANT 4516 / 6104, a TUNING
-    # build's override (variant_override() is the constant -1 in a release build)
-    (r"20bsr32_f32_cs2_kernelILb[01]ELi32ELi6ELi3ELb1ELb1ELb0ELb0ELb0ELb[01]EE", 4,
-     "ANT = false: variant 4516 only"),
-    (r"19bsr16_f16_cs_kernelILb[01]ELi2ELi4ELi0ELi48ELb0ELb1ELi256ELb0EE", 2,
-     "ANT = false: variant 6104 only"),
-]
-
 
 @pytest.fixture(scope="module")
 def trace() -> str:
@@ -62,34 +45,6 @@ def test_trace_matches_golden(trace):
     diff = [(i + 1, w, g) for i, (w, g) in enumerate(zip(want, got)) if w != g]
     assert not diff, "first differing line %d:\n  golden: %s\n  now:    %s" % diff[0]
     assert len(got) == len(want), f"{len(got)} lines, golden has {len(want)}"
-
-
-def kernel_key(symbol: str) -> str:
-    """The symbol up to the end of its nested name: namespace, kernel name and template
-    arguments. The parameter list after it is left out: its substitutions (S2_ ...) are
-    numbered differently once the symbol sits inside the tag's own template argument."""
-    assert symbol.startswith("_ZN"), symbol
-    i, depth = 3, 0
-    while True:
-        c = symbol[i]
-        if c.isdigit():  # <length><identifier>
-            j = i
-            while symbol[j].isdigit():
-                j += 1
-            i = j + int(symbol[i:j])
-        elif c == "I":
-            depth, i = depth + 1, i + 1
-        elif c == "L":  # a literal: L<type><value>E
-            i = symbol.index("E", i) + 1
-        elif symbol.startswith("DF", i):  # _Float16 (DF16_)
-            i = symbol.index("_", i) + 1
-        elif c == "E":
-            i += 1
-            if depth == 0:
-                return symbol[:i]
-            depth -= 1
-        else:  # a one-letter builtin type
-            i += 1
 
 
 def test_kernel_key():

@@ -486,8 +486,12 @@ def test_colmajor_c_past_the_tile_grid_limit(device, pad, beta):
     C0 = t["C0"]
     init = C0 if beta != 0.0 else np.full_like(C0, np.nan)
     dC, chk = framed(np.ascontiguousarray(init.T), m + pad, 0)
-    _ops().csrmm(drp, dci, dv, dB, m=m, n=n, k=k, ldb=n, C=dC, ldc=m + pad,
-                 order_c=_ops().ORDER_COL, beta=beta)
+    with _ops().default_handle().launch_record() as rec:
+        _ops().csrmm(drp, dci, dv, dB, m=m, n=n, k=k, ldb=n, C=dC, ldc=m + pad,
+                     order_c=_ops().ORDER_COL, beta=beta)
+    # the flat-grid transpose (FLAT = true), and not the tile-grid one
+    assert [k for k in rec if "transpose4_kernel" in k] == \
+        ["_ZN12_GLOBAL__N_117transpose4_kernelILb1EEEviiPKfiPfifj"], rec
     got = chk(f"ldc = m + {pad}, beta = {beta}: C").T
     want = t["row"] if beta == 0.0 else t["row"] + C0
     assert want.dtype == np.float32

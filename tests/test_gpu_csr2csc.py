@@ -71,7 +71,18 @@ def test_device_equals_numpy_and_host(device, name):
         # and take the three-launch scan, as the column counts of skew and wide do
         assert ci.size > 16 * 8192 and n > 4096
     v = values(ci.size, 4)
-    got = _host(_ops().csr2csc(*_dev(rp, ci, v), m=m, n=n, return_perm=True))
+    with _ops().default_handle().launch_record() as rec:
+        got = _host(_ops().csr2csc(*_dev(rp, ci, v), m=m, n=n, return_perm=True))
+    # the claims above, from the launch record: one digit_scatter_kernel per radix pass;
+    # a scan past 4096 counts is chunk_sum_kernel + scan_kernel + chunk_scan_kernel (the
+    # column counts once, the (digit, tile) counts once per pass), else scan_kernel alone
+    passes = {"n1": 0, "n200": 1, "n256": 1, "skew": 3, "wide": 4}.get(name, 2)
+    chunked = int(n > 4096) + passes * int(256 * -(-ci.size // 8192) > 4096)
+    count = lambda kernel: sum(kernel in k for k in rec)  # noqa: E731
+    assert count("digit_scatter_kernel") == passes == count("digit_count_kernel"), rec
+    assert count("chunk_sum_kernel") == chunked == count("chunk_scan_kernel"), rec
+    assert count("11scan_kernelE") == 1 + passes, rec
+    assert chunked == {"n4097": 1, "skew": 4, "wide": 1}.get(name, 0)
     ref, host = _ref(name, 4)
     _same(got, ref, True, name)
     for a, b, nm in zip(got, host, ("colptr", "rowind", "val", "perm")):

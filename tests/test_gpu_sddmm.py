@@ -54,7 +54,11 @@ def test_device_equals_host(device, name, n):
     # beta == 0: out is never read (a NaN there would spread), and in a view only the
     # view's positions are written
     nan = np.full(ci.size, np.nan, np.float32)
-    got = ops.sddmm(d_rp, d_ci, dX, dY, m=m, n=n, k=k, out=_dev(nan)[0])
+    with ops.default_handle().launch_record() as rec:
+        got = ops.sddmm(d_rp, d_ci, dX, dY, m=m, n=n, k=k, out=_dev(nan)[0])
+    # N_WIDE is past the lane-group kernel's four chunks per lane: the whole-wave kernel
+    assert len(rec) == (1 if nnz else 0), rec
+    assert all(("17sddmm_wide_kernelI" in key) == (n == N_WIDE) for key in rec), rec
     want = prep.sddmm(m, n, k, rp, ci, X, Y, out=nan.copy())
     assert not np.isnan(want[p0:p0 + nnz]).any()
     _same(got, want, f"{name} n={n}")
