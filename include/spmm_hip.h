@@ -119,7 +119,8 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *   Capturable, and tested so: spmm_csrmm_ex_f32 / _f16 / _f64 (any
  *     spmm_set_csr_waves_per_cu), spmm_csrmm_hot_f32, spmm_bsrmm_ex_f32 / _f16
  *     / _f64 (SPMM_BSR_SMALL_GROUPED included), spmm_hybrid_csrmm_f32 /
- *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 (which keeps
+ *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 and
+ *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 (which keep
  *     nothing in the handle's buffers), and the filling call of a group
  *     analysis. The setters of handle options are host-only: what they set is
  *     baked into the launches captured after them.
@@ -179,7 +180,9 @@ spmm_status_t spmm_get_launch_record(spmm_handle_t handle, const char** ids, int
                                      int* count);
 
 /* Tuning knob for the CSR merge-path kernel: resident waves per CU the grid
- * is sized for (0 = default). */
+ * is sized for (0 = default). The edge softmax's kernel takes it too: that many
+ * waves per CU share the rows, however few each then gets (its bits are the
+ * row's at any grid). */
 spmm_status_t spmm_set_csr_waves_per_cu(spmm_handle_t handle, int waves_per_cu);
 /* The target a handle without that setting sizes a CSR launch's grid for: 16
  * waves per CU, 12 from 2^20 rows on the plain kernel (hot != 0: the
@@ -732,6 +735,77 @@ spmm_status_t spmm_sddmm_csr_f32(spmm_handle_t handle, int m, int n, int k, int 
                                  const int* csrRowPtr, const int* csrColInd,
                                  spmm_index_base_t base, const float* X, int ldx, const float* Y,
                                  int ldy, float beta, float* outVal);
+
+/* Edge softmax (DGL's edge_softmax, PyG's softmax(src, ptr=...); no reference
+ * counterpart): the softmax of x over the positions of every CSR row, the second step
+ * of graph attention between spmm_sddmm_csr_f32 (the logits) and the CSR product on
+ * those values. For every row r with the positions [a, b) = [csrRowPtr[r],
+ * csrRowPtr[r + 1]) - base:
+ *     mx   = max of x[a..b)              (fmaxf: a NaN operand is dropped)
+ *     t[p] = x[p] - mx                   (one fp32 subtraction)
+ *     e[p] = EXP(t[p])
+ *     s    = SUM(e[a..b))
+ *     y[p] = e[p] / s                    (IEEE fp32 division)
+ * and the backward, from y and g = dloss/dy:
+ *     d     = SUM over the row of y[p] * g[p], each chain acc = fma(y[p], g[p], acc)
+ *     gx[p] = y[p] * (g[p] - d)          (the difference and the product rounded apart)
+ *   x, y (g, gx) hold nnz floats and share the pattern's index, as csrColInd and outVal
+ *     of spmm_sddmm_csr_f32 do; csrRowPtr[0] may exceed the base (a view): positions
+ *     outside [csrRowPtr[0], csrRowPtr[m]) - base are never written. Empty rows write
+ *     nothing. The column indices are not needed.
+ *   The rule: the bits of a row's outputs depend on the row's own values alone, never
+ *     on the grid, the worker count, the row's place, the other rows, a setting of the
+ *     handle or the entry point (device = host, bit for bit).
+ *       EXP (csrc/softmax_rule.hpp, one text for host and device): NaN -> NaN;
+ *       t < -64 (-inf included) -> exactly +0; t == 0 -> exactly 1.0f; otherwise
+ *       k = rint(t * log2(e)), r = fma(k, -ln2_lo, fma(k, -ln2_hi, t)), a degree-7 Horner
+ *       polynomial of exp(r) in FMAs, and the scaling by 2^k on the exponent bits. Only
+ *       fp32 +, *, FMA, rint, conversions and integer operations: no libm exp, no
+ *       hardware approximation. Every nonzero term is a normal number, and so is every
+ *       nonzero quotient, so no result depends on a denormal mode.
+ *       SUM: the row is cut into pieces of 1024 positions counted from its start. In a
+ *       piece, chain c (0 .. 63) takes the positions = c (mod 64) in ascending order,
+ *       starting from +0; the 64 chains fold in the butterfly acc_l + acc_(l xor s),
+ *       s = 1, 2, ..., 32 (pairwise over adjacent chains, level by level); the piece
+ *       sums are added one after the other in ascending order, starting from +0. A row
+ *       of at most 64 positions is a pairwise tree over its terms padded with +0.
+ *   Special values follow from the rule: a NaN, a +inf or nothing but -inf in a row
+ *     makes every output of that row NaN; a -inf (or anything more than 64 below the
+ *     maximum) beside finite values gives exactly +0; a row of one finite value gives
+ *     exactly 1.0f.
+ *   Aliasing: y may be exactly x, gx may be exactly g; any other overlap is the
+ *     caller's fault.
+ *   Checks, in order: negative m or nnz, another base, or a NULL pointer with nnz > 0
+ *     are SPMM_STATUS_INVALID_VALUE; m == 0 or nnz == 0 returns success at once. The
+ *     host forms also refuse (before they write anything) a decreasing row pointer,
+ *     csrRowPtr[0] below the base and csrRowPtr[m] - base above nnz.
+ * Host pointers, worker threads like the other host conversions. */
+spmm_status_t spmm_edge_softmax_csr_host_f32(int m, int nnz, const int* csrRowPtr,
+                                             spmm_index_base_t base, const float* x, float* y);
+spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrRowPtr,
+                                                 spmm_index_base_t base, const float* y,
+                                                 const float* g, float* gx);
+
+/* The two host forms on the device: the same contract and the same bits
+ * (tests/test_gpu_edge_softmax.py), device pointers, one kernel on the handle's stream
+ * (csrc/softmax_kernels.hip). Waves take equal shares of the merge path
+ * of rows and positions; lane groups of 4, 16 or 64 lanes (by the mean row length) take
+ * a row of up to 1024 positions each, and a longer row is done by the one workgroup
+ * that owns it, its pieces spread over that workgroup's waves. No workgroup waits for
+ * another; there are no atomics.
+ *   A NULL handle is SPMM_STATUS_NOT_INITIALIZED before the checks above. A bad row
+ *     pointer is the caller's fault: there is no device-side validation and no
+ *     read-back (positions are clamped to [0, nnz], rows to [0, m)).
+ *   The calls do not synchronise, take nothing from the handle's buffers (a repeat
+ *     allocates nothing) and may be captured into a graph; a replay re-reads the row
+ *     pointer and the values at the captured addresses. With kernel timing on, the
+ *     kernel is timed; with the launch record on, it is recorded. */
+spmm_status_t spmm_edge_softmax_csr_f32(spmm_handle_t handle, int m, int nnz,
+                                        const int* csrRowPtr, spmm_index_base_t base,
+                                        const float* x, float* y);
+spmm_status_t spmm_edge_softmax_bwd_csr_f32(spmm_handle_t handle, int m, int nnz,
+                                            const int* csrRowPtr, spmm_index_base_t base,
+                                            const float* y, const float* g, float* gx);
 
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's

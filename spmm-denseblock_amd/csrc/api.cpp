@@ -202,6 +202,30 @@ spmm_status_t spmm_sddmm_csr_f32(spmm_handle_t handle, int m, int n, int k, int 
                       beta, outVal);
 }
 
+spmm_status_t spmm_edge_softmax_csr_f32(spmm_handle_t handle, int m, int nnz,
+                                        const int* csrRowPtr, spmm_index_base_t base,
+                                        const float* x, float* y) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !x || !y)) return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  return launch_edge_softmax(handle, false, m, nnz, csrRowPtr, (int)base, x, nullptr, y);
+}
+
+spmm_status_t spmm_edge_softmax_bwd_csr_f32(spmm_handle_t handle, int m, int nnz,
+                                            const int* csrRowPtr, spmm_index_base_t base,
+                                            const float* y, const float* g, float* gx) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !y || !g || !gx)) return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  return launch_edge_softmax(handle, true, m, nnz, csrRowPtr, (int)base, y, g, gx);
+}
+
 spmm_status_t spmm_csr_hot_analysis(spmm_handle_t handle, int n, int k, int nnz,
                                     const int* csrColInd, spmm_index_base_t base,
                                     long long hotBytes, int* csrColIndHot) {

@@ -187,6 +187,11 @@ size_t csrmm_carry_bytes(spmm_context* ctx, int m, int n);
 spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* rowptr,
                            const int* colind, int base, const float* X, int ldx, const float* Y,
                            int ldy, float alpha, float beta, float* out);
+// spmm_edge_softmax_csr_f32 (u = x, v unused, o = y) and spmm_edge_softmax_bwd_csr_f32
+// (bwd; u = y, v = g, o = gx) (softmax_kernels.hip): one launch, no workspace; o may be u
+// (forward) or v (backward)
+spmm_status_t launch_edge_softmax(spmm_context* ctx, bool bwd, int m, int nnz, const int* rowptr,
+                                  int base, const float* u, const float* v, float* o);
 
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_util.hpp"
+#include "softmax_rule.hpp"
 
 #include "spmm_hip.h"
 
@@ -355,6 +356,111 @@ spmm_status_t spmm_sddmm_csr_host_f32(int m, int n, int k, int nnz, float alpha,
       while (p >= (int64_t)csrRowPtr[r + 1] - ba) ++r;
       const float d = sddmm_dot(X + (int64_t)r * ldx, Y + (int64_t)(csrColInd[p] - ba) * ldy, n, G);
       outVal[p] = beta == 0.f ? alpha * d : __builtin_fmaf(beta, outVal[p], alpha * d);
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The SUM of the edge softmax's rule (include/spmm_hip.h) over a row of L
+// positions: pieces of 1024 positions from the row's start; in a piece chain c of 64 takes
+// the positions = c (mod 64) in ascending order from +0 (term(acc, q) appends position q),
+// the chains fold pairwise over adjacent chains, level by level (the butterfly
+// acc_l + acc_(l xor s), s = 1, 2, ..., 32), and the piece sums are added in ascending
+// order.
+template <typename Term>
+inline float softmax_row_sum(int64_t L, Term term) {
+  constexpr int C = spmm_rule::kSoftmaxChains, P = spmm_rule::kSoftmaxPiece;
+  float s = 0.f;
+  for (int64_t q0 = 0; q0 < L; q0 += P) {
+    float acc[C];
+    for (int c = 0; c < C; ++c) {
+      float a = 0.f;
+      for (int64_t q = q0 + c; q < std::min<int64_t>(q0 + P, L); q += C) a = term(a, q);
+      acc[c] = a;
+    }
+    for (int w = C; w > 1; w >>= 1)
+      for (int l = 0; l < w / 2; ++l) acc[l] = acc[2 * l] + acc[2 * l + 1];
+    s += acc[0];
+  }
+  return s;
+}
+
+// The checks the two host forms share (the order of spmm_sddmm_csr_host_f32's); *done:
+// nothing to do.
+spmm_status_t softmax_host_check(int m, int nnz, const int* rp, spmm_index_base_t base,
+                                 bool null_ptr, bool* done) {
+  *done = true;
+  if (m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!rp || null_ptr)) return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)rp[0] - ba, p1 = (int64_t)rp[m] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (rp[r + 1] < rp[r]) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  *done = false;
+  return SPMM_STATUS_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The edge softmax and its backward on the host: the written rule in executable form (the
+// device entries equal them bit for bit). Workers take equal shares of the rows; an output
+// depends on its own row alone, so the worker count cannot change a bit. y may be x, gx
+// may be g: a row's inputs are read completely before its first output is written, except
+// the position's own.
+spmm_status_t spmm_edge_softmax_csr_host_f32(int m, int nnz, const int* csrRowPtr,
+                                             spmm_index_base_t base, const float* x, float* y) {
+  bool done;
+  const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !x || !y, &done);
+  if (done) return st;
+  const int ba = (int)base;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, L = (int64_t)csrRowPtr[r + 1] - ba - a;
+      const float* xr = x + a;
+      float mx = -__builtin_inff();
+      for (int64_t q = 0; q < L; ++q) mx = __builtin_fmaxf(mx, xr[q]);
+      const float s = softmax_row_sum(L, [&](float acc, int64_t q) {
+        return acc + spmm_rule::softmax_exp(xr[q] - mx);
+      });
+      for (int64_t q = 0; q < L; ++q) y[a + q] = spmm_rule::softmax_exp(xr[q] - mx) / s;
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrRowPtr,
+                                                 spmm_index_base_t base, const float* y,
+                                                 const float* g, float* gx) {
+  bool done;
+  const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !y || !g || !gx, &done);
+  if (done) return st;
+  const int ba = (int)base;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, L = (int64_t)csrRowPtr[r + 1] - ba - a;
+      const float* yr = y + a;
+      const float* gr = g + a;
+      const float d = softmax_row_sum(L, [&](float acc, int64_t q) {
+        return __builtin_fmaf(yr[q], gr[q], acc);
+      });
+      for (int64_t q = 0; q < L; ++q) {
+        const float diff = gr[q] - d;
+        gx[a + q] = yr[q] * diff;
+      }
     }
   });
   return SPMM_STATUS_SUCCESS;

@@ -15,6 +15,13 @@ own pattern.
     w = edge_weights(...)                         # nnz floats, requires grad
     H1 = spmm(A, H, val=w)                        # w replaces A.val for this product
     H1.sum().backward()                           # w.grad[p] = <dH1[row(p)], H[col(p)]>
+
+edge_softmax and sddmm close the attention chain on a fixed pattern: the logits
+(ops.sddmm, with gradients for X and Y from two CSR products), their softmax over every
+row's positions (ops.edge_softmax / ops.edge_softmax_bwd), and the product on them:
+
+    a = edge_softmax(A, sddmm(A, H, H))           # nnz attention weights
+    H1 = spmm(A, H, val=a)                        # backpropagates to H on all three paths
 """
 from __future__ import annotations
 
@@ -148,4 +155,75 @@ def spmm(A: CsrMatrix, B: torch.Tensor, val: torch.Tensor | None = None) -> torc
     return _SpmmVal.apply(B, val, A)
 
 
-__all__ = ["CsrMatrix", "spmm"]
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        y = ops.edge_softmax(A.rowptr, x.detach().contiguous(), m=A.m)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y: torch.Tensor):
+        (y,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return ops.edge_softmax_bwd(ctx.A.rowptr, y, grad_y.contiguous(), m=ctx.A.m), None
+
+
+def edge_softmax(A: CsrMatrix, x: torch.Tensor) -> torch.Tensor:
+    """y = the softmax of x over the positions of every row of A's pattern
+    (ops.edge_softmax; x: float32, nnz entries, one head). The forward saves y; the
+    backward is ops.edge_softmax_bwd(A.rowptr, y, grad_y): both a function of the row's
+    values alone, so two runs give the same gradient bits."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("edge_softmax: A must be a CsrMatrix")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda:
+        raise TypeError("edge_softmax: x must be a float32 tensor on a HIP device")
+    if x.dim() != 1 or x.numel() != A.colind.numel():
+        raise ValueError(f"edge_softmax: x must hold the pattern's {A.colind.numel()} values, "
+                         f"got {tuple(x.shape)}")
+    return _EdgeSoftmax.apply(x, A)
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, Y: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        X, Y = X.detach().contiguous(), Y.detach().contiguous()
+        ctx.save_for_backward(X, Y)
+        return ops.sddmm(A.rowptr, A.colind, X, Y, m=A.m, n=X.shape[1], k=A.k)
+
+    @staticmethod
+    def backward(ctx, ge: torch.Tensor):
+        A = ctx.A
+        X, Y = ctx.saved_tensors
+        ge = ge.contiguous()
+        grad_X = grad_Y = None
+        if ctx.needs_input_grad[0]:
+            grad_X = _product(A, Y, ge)
+        if ctx.needs_input_grad[1]:
+            grad_Y = _product(A.t(), X, torch.index_select(ge, 0, A.t_perm()))
+        return grad_X, grad_Y, None
+
+
+def sddmm(A: CsrMatrix, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """e[p] = <X[row(p), :], Y[col(p), :]> on A's pattern (ops.sddmm; X: m x n, Y: k x n),
+    with gradients for X and Y built from the CSR product, ge = the gradient of e:
+    grad_X = ops.csrmm on (A's pattern, values ge) applied to Y, and grad_Y = ops.csrmm on
+    A.t()'s pattern with the values ge[A.t_perm()] applied to X. Each is computed only
+    when it is needed: the transpose is not built for grad_X alone. X may be Y (the edge
+    logits <h_i, h_j>); autograd then adds the two."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("sddmm: A must be a CsrMatrix")
+    for t, rows, nm in ((X, A.m, "X"), (Y, A.k, "Y")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+            raise TypeError(f"sddmm: {nm} must be a float32 tensor on a HIP device")
+        if t.dim() != 2 or t.shape[0] != rows:
+            raise ValueError(f"sddmm: {nm} must be ({rows}, n), got {tuple(t.shape)}")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError("sddmm: X and Y differ in their column count")
+    return _Sddmm.apply(X, Y, A)
+
+
+__all__ = ["CsrMatrix", "spmm", "edge_softmax", "sddmm"]

@@ -12,6 +12,8 @@ through the C ABI. The functions mirror the reference's operator interfaces:
   csrmm_f16(...) / gespmm_csrmm_f16(...)
                       csrmm / gespmm_csrmm with fp16 A/B, fp32 accumulate and C
   sddmm(...)          cusparseSDDMM's shape on a CSR pattern: out[p] = <X[row(p)], Y[col(p)]>
+  edge_softmax(...) / edge_softmax_bwd(...)
+                      softmax over the positions of every CSR row (DGL's edge_softmax)
 """
 from __future__ import annotations
 
@@ -267,6 +269,55 @@ def sddmm(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: torch.
     check(lib().spmm_sddmm_csr_f32(h.raw, m, n, k, colind.numel(), alpha, _ptr(rowptr),
                                    _ptr(colind), base, _ptr(X), ldx, _ptr(Y), ldy, beta,
                                    _ptr(out)), "spmm_sddmm_csr_f32")
+    return out
+
+
+def _edge_softmax_args(where: str, rowptr: torch.Tensor, m: int | None, arrays, out):
+    _need(rowptr, torch.int32, "rowptr")
+    m = rowptr.numel() - 1 if m is None else m
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"{where}: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    nnz = arrays[0][1].numel()
+    for nm, t in arrays:
+        _need(t, torch.float32, nm)
+        if t.dim() != 1 or t.numel() != nnz:
+            raise ValueError(f"{where}: {nm} must be 1-D with the pattern's {nnz} entries (one "
+                             f"head; loop over the heads of a contiguous [H, nnz] layout)")
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=rowptr.device)
+    _need(out, torch.float32, "out")
+    if out.dim() != 1 or out.numel() != nnz:
+        raise ValueError(f"{where}: out must be 1-D with the pattern's {nnz} entries")
+    return m, nnz, out
+
+
+def edge_softmax(rowptr: torch.Tensor, x: torch.Tensor, *, m: int | None = None, base: int = 0,
+                 out: torch.Tensor | None = None, handle: Handle | None = None) -> torch.Tensor:
+    """Softmax of x over the positions of every CSR row (spmm_edge_softmax_csr_f32; DGL's
+    edge_softmax): x holds nnz fp32 values indexed like colind, out[p] = exp(x[p] - max of
+    p's row) / the row's sum. out: default a new tensor, may be x itself (in place); with
+    a rowptr that is a view only the view's positions are written. One kernel on the
+    handle's stream: no synchronisation, no workspace, no atomics, capturable. The bits
+    are a function of the row's values alone (the rule of include/spmm_hip.h) and equal
+    prep.edge_softmax's."""
+    m, nnz, out = _edge_softmax_args("edge_softmax", rowptr, m, (("x", x),), out)
+    h = handle or default_handle()
+    check(lib().spmm_edge_softmax_csr_f32(h.raw, m, nnz, _ptr(rowptr), base, _ptr(x), _ptr(out)),
+          "spmm_edge_softmax_csr_f32")
+    return out
+
+
+def edge_softmax_bwd(rowptr: torch.Tensor, y: torch.Tensor, g: torch.Tensor, *,
+                     m: int | None = None, base: int = 0, out: torch.Tensor | None = None,
+                     handle: Handle | None = None) -> torch.Tensor:
+    """The backward of edge_softmax (spmm_edge_softmax_bwd_csr_f32): from y = the forward's
+    output and g = the gradient of y, out[p] = y[p] * (g[p] - d) with d the sum of y * g
+    over p's row. out may be g itself. The same kernel in its second mode, the same
+    promises; the bits equal prep.edge_softmax_bwd's."""
+    m, nnz, out = _edge_softmax_args("edge_softmax_bwd", rowptr, m, (("y", y), ("g", g)), out)
+    h = handle or default_handle()
+    check(lib().spmm_edge_softmax_bwd_csr_f32(h.raw, m, nnz, _ptr(rowptr), base, _ptr(y), _ptr(g),
+                                              _ptr(out)), "spmm_edge_softmax_bwd_csr_f32")
     return out
 
 
@@ -815,5 +866,5 @@ class MultiGPU:
 
 
 __all__ = ["coo2csr", "MultiGPU", "csr2bsr", "csr2csc", "bsr2csr", "Handle", "hybrid_csrmm", "default_handle", "gespmm_csrmm", "csrmm", "bsrmm", "bsrmm_f16",
-           "csrmm_f16", "gespmm_csrmm_f16", "sddmm",
+           "csrmm_f16", "gespmm_csrmm_f16", "sddmm", "edge_softmax", "edge_softmax_bwd",
            "SpmmError", "ORDER_ROW", "ORDER_COL"]

@@ -2,6 +2,7 @@
 
 Thin wrappers over the C ABI of libspmm_hip.so:
   csr2bsr / bsr2csr / csr2csc / sddmm / calculate_nnzb / partition_rows   (include/spmm_hip.h)
+  edge_softmax / edge_softmax_bwd                                        (include/spmm_hip.h)
   rng_seed / random_array / random_csr / random_bsr /
   load_csr / dump_csr / load_graph / save_csr_bin / load_csr_bin / load_csr_cached /
   powerlaw_csr / community_csr                                  (include/spmm_host.h)
@@ -142,6 +143,47 @@ def sddmm(m: int, n: int, k: int, rowptr, colind, X, Y, *, ldx: int | None = Non
     check(lib().spmm_sddmm_csr_host_f32(m, n, k, colind.size, alpha, _p(rowptr), _p(colind), base,
                                         _p(ops_[0]), ldx, _p(ops_[1]), ldy, beta, _p(out)),
           "spmm_sddmm_csr_host_f32")
+    return out
+
+
+def _softmax_args(where: str, rowptr, m, arrays, out):
+    rowptr = _i32(rowptr)
+    m = rowptr.size - 1 if m is None else m
+    if m < 0 or rowptr.size != m + 1:
+        raise ValueError(f"{where}: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    nnz = arrays[0][1].size
+    for nm, a in arrays:
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 1 or \
+                not a.flags.c_contiguous or a.size != nnz:
+            raise TypeError(f"{where}: {nm} must be a contiguous 1-D float32 array of nnz entries")
+    if out is None:
+        out = np.zeros(nnz, dtype=np.float32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 1 or \
+            not out.flags.c_contiguous or out.size != nnz:
+        raise TypeError(f"{where}: out must be a contiguous 1-D float32 array of nnz entries")
+    return rowptr, m, nnz, out
+
+
+def edge_softmax(rowptr, x, *, m: int | None = None, base: int = 0, out=None) -> np.ndarray:
+    """spmm_edge_softmax_csr_host_f32: out[p] = softmax of x over the positions of p's CSR
+    row, by the rule of include/spmm_hip.h (the bits of ops.edge_softmax). x: float32 of
+    nnz entries, indexed like colind. out: the same shape (default zeros; returned; may be
+    x itself). rowptr[0] may exceed `base`: positions outside the view are left alone."""
+    rowptr, m, nnz, out = _softmax_args("edge_softmax", rowptr, m, (("x", x),), out)
+    check(lib().spmm_edge_softmax_csr_host_f32(m, nnz, _p(rowptr), base, _p(x), _p(out)),
+          "spmm_edge_softmax_csr_host_f32")
+    return out
+
+
+def edge_softmax_bwd(rowptr, y, g, *, m: int | None = None, base: int = 0,
+                     out=None) -> np.ndarray:
+    """spmm_edge_softmax_bwd_csr_host_f32: out[p] = y[p] * (g[p] - d(row of p)),
+    d = the row's sum of y * g, by the rule of include/spmm_hip.h (the bits of
+    ops.edge_softmax_bwd). out may be g itself."""
+    rowptr, m, nnz, out = _softmax_args("edge_softmax_bwd", rowptr, m, (("y", y), ("g", g)), out)
+    check(lib().spmm_edge_softmax_bwd_csr_host_f32(m, nnz, _p(rowptr), base, _p(y), _p(g),
+                                                   _p(out)),
+          "spmm_edge_softmax_bwd_csr_host_f32")
     return out
 
 
