@@ -86,29 +86,18 @@ struct ColCursor {
 // ---------------------------------------------------------------------------
 // bs = 32 fp32 MFMA. Block = 4 waves, each wave a 32-column slice.
 // ---------------------------------------------------------------------------
-// VAR (tuning variants; kBsr32Default is the shipped one):
-//   VAR & 3  pipeline: 0 = prefetch block k+1 into a second register set,
-//            1 = fixed-role double buffer, 2 = load-use (no prefetch; the
-//            other resident waves hide the latency)
-//   VAR & 4  XCD-aware block-row order (neighbouring block rows share an L2)
-//   VAR >> 3 minimum waves per SIMD requested from the register allocator
-//            (0 = no bound). Measured on the reddit stand-in:
-//            this kernel is bound by B-panel traffic beyond L2, so resident
-//            waves (memory-level parallelism) decide its speed.
-template <bool ROWDIR, bool BROW, bool CROW, int VAR>
-__global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr32_f32_mfma_kernel(
+// Five waves per SIMD are requested from the register allocator. Measured on the reddit
+// stand-in: this kernel is bound by B-panel traffic beyond L2, so resident
+// waves (memory-level parallelism) decide its speed. The pipelines and the XCD-aware
+// block-row order that were swept against it are in DESIGN.md §4 "Variant history".
+template <bool ROWDIR, bool BROW, bool CROW>
+__global__ __launch_bounds__(256, 5) void bsr32_f32_mfma_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const float* __restrict__ val, const float* __restrict__ B, int ldb, float alpha, float beta,
     float* __restrict__ C, int ldc) {
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
-  int br = blockIdx.x;
-  if constexpr ((VAR & 4) != 0) {
-    // Round-robin dispatch puts block b on XCD b % 8: give each XCD a
-    // contiguous range of block rows instead (bijective for any mb).
-    const int q = mb / 8, rem = mb % 8, x = br % 8, i = br / 8;
-    br = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + i;
-  }
+  const int br = blockIdx.x;
   const int j0 = (blockIdx.y * (blockDim.x >> 6) + wv) * 32;
   if (j0 >= n) return;
   const int r = lane & 31;
@@ -156,37 +145,19 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr32_f32_mf
     for (int s = 0; s < 16; ++s)
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s], fb[s], acc, 0, 0, 0);
   };
-  // Two fragment buffers with fixed roles (loop unrolled by 2): block k+1's
-  // loads are in flight while block k's MFMAs issue, and no register copy
-  // ties the MFMAs to the loads just issued. Prefetches are unconditional
-  // (index clamped to the last block; the tail re-reads it and skips the
-  // MFMAs), so no branch around a load makes hipcc's counted waits collapse.
+  // Block k+1's fragments are loaded into a second register set while block k's MFMAs
+  // issue, then copied over.
   float a0[16], b0[16], a1[16], b1[16];
-  const int kl = k1 - 1;
   if (k0 < k1) {
     load_frags(k0, a0, b0);
     settle(a0);
     settle(b0);
   }
-  if constexpr ((VAR & 3) == 1) {
-    for (int k = k0; k < k1; k += 2) {
-      load_frags(min(k + 1, kl), a1, b1);
-      mfma16(a0, b0);
-      load_frags(min(k + 2, kl), a0, b0);
-      if (k + 1 < k1) mfma16(a1, b1);
-    }
-  } else if constexpr ((VAR & 3) == 2) {
-    for (int k = k0; k < k1; ++k) {
-      if (k > k0) load_frags(k, a0, b0);
-      mfma16(a0, b0);
-    }
-  } else {
-    for (int k = k0; k < k1; ++k) {
-      if (k + 1 < k1) load_frags(k + 1, a1, b1);
-      mfma16(a0, b0);
+  for (int k = k0; k < k1; ++k) {
+    if (k + 1 < k1) load_frags(k + 1, a1, b1);
+    mfma16(a0, b0);
 #pragma unroll
-      for (int s = 0; s < 16; ++s) { a0[s] = a1[s]; b0[s] = b1[s]; }
-    }
+    for (int s = 0; s < 16; ++s) { a0[s] = a1[s]; b0[s] = b1[s]; }
   }
 
   if (!jok) return;
@@ -237,7 +208,7 @@ constexpr int waitcnt_vm_lgkm0(int n) { return (n & 15) | (7 << 4) | ((n >> 4) <
 // (a merge-path cut over the 33 row pointers, one ballot per wave). A wave
 // walks its rows with wave-uniform (scalar) colind/val loads, lanes across the
 // 128 columns (one float2 of each B row per lane, 512 B per wave-instruction),
-// HB (24) entries in flight per batch, one sequential FMA chain per element in CSR
+// kHybBatch entries in flight per batch, one sequential FMA chain per element in CSR
 // order, and writes each row once:
 //   C = epi(tile, alpha, beta, C) + alpha * remainder
 // which is the two-launch result (BSR kernel, then the CSR kernel with
@@ -246,7 +217,8 @@ constexpr int waitcnt_vm_lgkm0(int n) { return (n & 15) | (7 << 4) | ((n >> 4) <
 // phases on the same CU.
 constexpr int kHybTs = 136;  // tile row stride (floats): the two half-waves' rows
                              // land 32 banks apart when the tile is written
-template <int D, int kHybBatch, bool PAIR = false>
+constexpr int kHybBatch = 24;  // remainder gathers in flight per wave
+template <bool PAIR>
 __device__ __forceinline__ void hyb_remainder(float* smem, const f32x16& acc, const f32x16& acc1,
                                               int br, int jt,
                                               int n, const int* __restrict__ rrp,
@@ -348,11 +320,13 @@ __device__ __forceinline__ void hyb_remainder(float* smem, const f32x16& acc, co
 // HYB (the fused hybrid, §4a): after the block loop the workgroup adds its
 // 32 rows' CSR remainder (rrp/rci/rv, m rows) — see hyb_remainder below.
 // Only CROW is instantiated with HYB.
-// XM: block-row order across the 8 XCDs (dispatch puts workgroup b on XCD
+// xm: block-row order across the 8 XCDs (dispatch puts workgroup b on XCD
 // b % 8). 0 = as dispatched; 1 = each XCD a contiguous eighth (neighbouring
-// block rows share that XCD's L2); XM >= 2 = chunks of XM block rows dealt
+// block rows share that XCD's L2); xm >= 2 = chunks of xm block rows dealt
 // round-robin to the XCDs (L2 locality inside a chunk, and a heavy region of
-// the matrix spread over all XCDs instead of landing on one).
+// the matrix spread over all XCDs instead of landing on one). The bs = 32
+// kernels without an order array use chunks of kXcdChunk32 block rows.
+constexpr int kXcdChunk32 = 32;
 __device__ __forceinline__ int xcd_block_row(int b, int mb, int xm) {
   if (xm == 1) {
     const int q = mb / 8, rem = mb % 8, x = b % 8, i = b / 8;
@@ -417,23 +391,23 @@ __device__ __forceinline__ f32x16 split_mfma6(const bf16x8& ah, const bf16x8& ah
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
-// HB: remainder gathers in flight per wave in the fused hybrid (HYB).
-// PAIR (with SPLIT, row-major C): split-K over wave pairs. Wave w takes k half
+// PAIR (SPLIT with row-major C): split-K over wave pairs. Wave w takes k half
 // w & 1 of every block for 64 output columns (two tiles), so it splits 8 A
 // values per lane per block instead of 16; the pair's partial tiles are added
 // through LDS once per block row.
-template <bool CROW, int D, int XM, bool HYB = false, int HB = 24, bool SPLIT = false,
-          bool PAIR = false>
+template <bool CROW, bool HYB, bool SPLIT>
 __global__ __launch_bounds__(256) void bsr32_f32_lds_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const float* __restrict__ val, const float* __restrict__ B, int ldb, float alpha, float beta,
     float* __restrict__ C, int ldc, const int* __restrict__ rrp, const int* __restrict__ rci,
     const float* __restrict__ rv, int m, const int* __restrict__ order) {
+  constexpr int D = 2;  // stages: the copies of block k + 1 are issued at block k
+  constexpr bool PAIR = SPLIT && CROW;
   constexpr int kStage = 1024 + 32 * 128;  // floats: A block + B panel (20 KB)
   __shared__ __attribute__((aligned(16))) float smem[D * kStage];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
-  const int br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, XM);
+  const int br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, kXcdChunk32);
   const int jt = blockIdx.y * 128;  // first output column of the workgroup
   const int k0 = rowptr[br], k1 = rowptr[br + 1];
   if (!HYB && k0 >= k1) {  // empty block row: C = beta * C (alpha * 0)
@@ -470,7 +444,6 @@ __global__ __launch_bounds__(256) void bsr32_f32_lds_kernel(
                                        0, 0);
   };
 
-  static_assert(!PAIR || (SPLIT && CROW), "PAIR needs SPLIT and row-major C");
   const int r = lane & 31, h = lane >> 5;
   f32x16 acc, acc1;
 #pragma unroll
@@ -544,8 +517,7 @@ __global__ __launch_bounds__(256) void bsr32_f32_lds_kernel(
   }
 
   if constexpr (HYB) {
-    hyb_remainder<D, HB, PAIR>(smem, acc, acc1, br, jt, n, rrp, rci, rv, m, B, ldb, alpha, beta,
-                               C, ldc);
+    hyb_remainder<PAIR>(smem, acc, acc1, br, jt, n, rrp, rci, rv, m, B, ldb, alpha, beta, C, ldc);
     return;
   }
   if constexpr (PAIR) {
@@ -1007,7 +979,7 @@ __global__ __launch_bounds__(1024) void block_row_order_kernel(int mb, const int
 // offset c * ldb * 4 + column offset in the 32-bit VGPR offset (one s_mul and
 // one v_add per load instead of a 64-bit address on the scalar unit); needs
 // 32 * ldb * 4 < 2^31 (checked by the launcher).
-// PK: an item whose block has no second column left takes the first column
+// Packed items: an item whose block has no second column left takes the first column
 // of the next block (its A column from that block's slot, its B row from that
 // block's panel), so single-column blocks no longer make half-empty items.
 // The first column's A read is complete before the next block's A copy can
@@ -1052,8 +1024,7 @@ __device__ __forceinline__ bool panel_chosen(const unsigned long long* stat) {
   return stat[1] > 0 && stat[0] >= (unsigned long long)kPanelMin * stat[1];
 }
 
-template <bool CROW, int XM, int P, int NA, bool O32 = false, bool PK = false, bool ANT = false,
-          bool MSK = false, bool SUB = false, bool C64 = false>
+template <bool CROW, bool O32, bool ANT, bool MSK, bool SUB, bool C64>
 __global__ __launch_bounds__(64) void bsr32_f32_cs2_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const float* __restrict__ val, const float* __restrict__ B, int ldb, float alpha, float beta,
@@ -1061,15 +1032,16 @@ __global__ __launch_bounds__(64) void bsr32_f32_cs2_kernel(
     const int4* __restrict__ segs = nullptr, float* __restrict__ part = nullptr,
     const unsigned* __restrict__ masks = nullptr,
     const unsigned long long* __restrict__ gate = nullptr) {
-  static_assert(NA >= 2 && NA <= 4 && P >= 2 && P <= 16, "ring depths");
+  constexpr int P = 6;   // items in flight
+  constexpr int NA = 3;  // A ring slots
   // the panel probe chose bsr32_f32_panel_kernel for this matrix (same bits): nothing to do
   if (gate && panel_chosen(gate)) return;
   static_assert(!(SUB && MSK), "the analysed stream is bs 32 only");
   constexpr int DA = NA - 1;  // A blocks in flight ahead of the producer's block
   constexpr int LDA = SUB ? 64 : 32;  // row stride of a (sub-)block's values
-  // (column-major C reuses the LDS for a 128 x 36-float tile)
-  __shared__ __attribute__((aligned(16)))
-  float smem[MSK && CROW ? 4 : (CROW || NA * 1024 >= 128 * 36 ? NA * 1024 : 128 * 36)];
+  // (column-major C reuses the LDS for a 128 x 36-float tile, which is larger than the ring)
+  static_assert(NA * 1024 <= 128 * 36);
+  __shared__ __attribute__((aligned(16))) float smem[MSK && CROW ? 4 : (CROW ? NA * 1024 : 128 * 36)];
   const int lane = threadIdx.x;
   const int j = lane & 31, h = lane >> 5;
   // a segment of a block row (seg_build_kernel; row-major C only) or a whole row
@@ -1082,7 +1054,7 @@ __global__ __launch_bounds__(64) void bsr32_f32_cs2_kernel(
     k1 = sg.z;
     pidx = sg.w;
   } else {
-    br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, XM);
+    br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, kXcdChunk32);
     if constexpr (SUB) {  // virtual sub-block indices (above)
       k0 = 2 * rowptr[br >> 1];
       k1 = 2 * rowptr[(br >> 1) + 1];
@@ -1328,46 +1300,23 @@ __global__ __launch_bounds__(64) void bsr32_f32_cs2_kernel(
         if (m != 0u) {
           const int c0 = __builtin_ctz(m);
           m &= m - 1u;
-          if constexpr (PK) {
-            // first column: A read and B load now, from this block
+          // first column: A read and B load now, from this block
+          if constexpr (MSK)
+            load_acol(ra0[s], c0);
+          else
+            asm volatile("ds_read_b32 %0, %1" : "=&v"(ra0[s]) : "v"(acol(c0)) : "memory");
+          load_row(rb0[s], c0);
+          kind[s] = 1;
+          while (m == 0u && k + 1 < k1) advance();  // pair with the next block's first column
+          if (m != 0u) {
+            const int c1 = __builtin_ctz(m);
+            m &= m - 1u;
             if constexpr (MSK)
-              load_acol(ra0[s], c0);
-            else
-              asm volatile("ds_read_b32 %0, %1" : "=&v"(ra0[s]) : "v"(acol(c0)) : "memory");
-            load_row(rb0[s], c0);
-            kind[s] = 1;
-            while (m == 0u && k + 1 < k1) advance();  // pair with the next block's first column
-            if (m != 0u) {
-              const int c1 = __builtin_ctz(m);
-              m &= m - 1u;
-              if constexpr (MSK)
-                load_acol(ra1[s], c1);
-              else
-                asm volatile("ds_read_b32 %0, %1" : "=&v"(ra1[s]) : "v"(acol(c1)) : "memory");
-              load_row(rb1[s], c1);
-              kind[s] = 2;
-            }
-          } else {
-            int c1 = c0;
-            if (m != 0u) {
-              c1 = __builtin_ctz(m);
-              m &= m - 1u;
-            }
-            if constexpr (MSK) {
-              load_acol(ra0[s], c0);
               load_acol(ra1[s], c1);
-            } else {
-              asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3"
-                           : "=&v"(ra0[s]), "=&v"(ra1[s])
-                           : "v"(acol(c0)), "v"(acol(c1))
-                           : "memory");
-            }
-            load_row(rb0[s], c0);
-            kind[s] = 1;
-            if (c1 != c0) {
-              load_row(rb1[s], c1);
-              kind[s] = 2;
-            }
+            else
+              asm volatile("ds_read_b32 %0, %1" : "=&v"(ra1[s]) : "v"(acol(c1)) : "memory");
+            load_row(rb1[s], c1);
+            kind[s] = 2;
           }
           stamp[s] = nis;
         }
@@ -1570,12 +1519,13 @@ __global__ __launch_bounds__(256) void panel_probe_kernel(long long nnzb, int ns
 
 // SUB (bs 64): as the column stream's SUB form, one wave per 32-row half br of a block row,
 // walking the virtual 32 x 32 sub-blocks kk of its row (block kk / 2, column half kk % 2).
-template <bool CROW, bool C64, int D, bool SUB = false>
+template <bool CROW, bool C64, bool SUB>
 __global__ __launch_bounds__(64) void bsr32_f32_panel_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const float* __restrict__ val, const float* __restrict__ B, int ldb, float alpha, float beta,
     float* __restrict__ C, int ldc, const int* __restrict__ order,
     const unsigned long long* __restrict__ stat) {
+  constexpr int D = C64 ? SPMM_PANEL_D64 : SPMM_PANEL_D128;  // stages
   constexpr int TW = C64 ? 64 : 128;        // output columns of the wave
   constexpr int kStage = 1024 + 32 * TW;    // floats: A block + B panel
   constexpr int kOps = 4 + 32 * TW / 256;   // copies per block (16 B per lane each)
@@ -1584,7 +1534,7 @@ __global__ __launch_bounds__(64) void bsr32_f32_panel_kernel(
   if (!panel_chosen(stat)) return;
   const int lane = threadIdx.x;
   const int j = lane & 31, h = lane >> 5;
-  const int br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, 32);
+  const int br = order ? order[blockIdx.x] : xcd_block_row(blockIdx.x, mb, kXcdChunk32);
   const int jt = blockIdx.y * TW;
   const int k0 = SUB ? 2 * rowptr[br >> 1] : rowptr[br];
   const int k1 = SUB ? 2 * rowptr[(br >> 1) + 1] : rowptr[br + 1];
@@ -1809,11 +1759,18 @@ __device__ __forceinline__ int bsr16_swz(int row) {
 // from g_zero_row. The MFMAs are not skipped (see the loop). Copies per iteration:
 // P = 1 (A) + 2 (fp16) or 4 (fp32) (B).
 // ---------------------------------------------------------------------------
-template <typename T, bool CROW, int D = 2, int DA = D + 3, int WPE = 1, int COLS = 256>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void bsr16_cm_kernel(
+// Waves per SIMD asked of the register allocator: 8 for fp16 A/B, no bound (1) for fp32.
+template <typename T>
+constexpr int kBsr16CmWavesPerEu = sizeof(T) == 2 ? 8 : 1;
+
+template <typename T, bool CROW, int COLS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBsr16CmWavesPerEu<T>)))
+void bsr16_cm_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const T* __restrict__ val, const T* __restrict__ B, int ldb, float alpha, float beta,
     float* __restrict__ C, int ldc) {
+  constexpr int D = 2;   // B stages
+  constexpr int DA = 5;  // A ring slots
   constexpr int kEpc = 16 / sizeof(T);             // elements per 16-B chunk
   constexpr int kA = 256 * sizeof(T);              // A block bytes
   constexpr int kRowB = COLS * sizeof(T);          // B panel row bytes (COLS columns)
@@ -2087,40 +2044,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 // values to find them (no ds_read / ballot round trip), and the A values a block pushes
 // (lane (g, c): rows 4g .. 4g + 3 of column c, 8 contiguous bytes) come one pair of
 // blocks ahead into registers instead of an LDS ring: 2 KB less LDS per wave.
-template <bool CROW, int P, int NA, int DA, int CAP = 48, bool ANT = false, bool CST = false,
-          int COLS = 256, bool MSK = false>
+template <bool CROW, bool ANT, bool MSK>
 __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const _Float16* __restrict__ val, const _Float16* __restrict__ B, int ldb, float alpha,
     float beta, float* __restrict__ C, int ldc, const int* __restrict__ order,
     const unsigned* __restrict__ masks = nullptr, int ntt = 0) {
-  // COLS: output columns per wave (the launcher uses 256). 512 makes a stage row one whole
-  // 1-KB B row and serves all 512 columns with one A copy and one walk per block row; 128
-  // quarters the stage. Both pass the parity subset and lose on the products stand-in, K =
-  // 512: 4.37 ms at 512 (4 waves per CU by LDS) and 4.87 at 128 (4 tiles of A and walk per
-  // block row), against 3.77-3.89 at 256 (profiles/r03_cols_per_wave_ab.txt)
-  static_assert(COLS == 128 || COLS == 256 || COLS == 512, "columns per wave");
+  // COLS: output columns per wave. 512 made a stage row one whole 1-KB B row and served all
+  // 512 columns with one A copy and one walk per block row; 128 quartered the stage. Both
+  // passed the parity subset and lost on the products stand-in, K = 512: 4.37 ms at 512 (4
+  // waves per CU by LDS) and 4.87 at 128 (4 tiles of A and walk per block row), against
+  // 3.77-3.89 at 256 (profiles/r03_cols_per_wave_ab.txt)
+  constexpr int COLS = 256;
+  constexpr int P = 2;   // item stages
+  constexpr int NA = 4;  // A ring slots
+  constexpr int DA = 0;  // A pairs are copied DA + 2 blocks ahead of the producer
+  // pending-list capacity: 48 entries (64 needs a larger A-fragment buffer; 48 gives 8 waves
+  // per CU with NA = 4); a pair of blocks adds at most 32 to at most 15 pending
+  constexpr int CAP = 48;
   constexpr int kRowB = COLS * 2;     // bytes per stage row
   constexpr int kCh = COLS / 8;       // 16-B chunks per stage row
-  constexpr int kRpc = 1024 / kRowB;  // stage rows per copy (4, 2 or 1)
+  constexpr int kRpc = 1024 / kRowB;  // stage rows per copy
   constexpr int kCp = 16 / kRpc;      // copies per item
   // the pair copied at block kr (blocks kr + DA + 2, + 3) overwrites blocks
   // kr + DA + 2 - NA, + 3 - NA, which must be read already (< kr)
-  static_assert((NA & (NA - 1)) == 0 && DA % 2 == 0 && NA >= DA + 4 && P >= 2 && P <= 6,
-                "ring depths");
-  // pending-list capacity: 64 entries, or 48 (a smaller A-fragment buffer: 8 waves per CU
-  // with NA = 4); a pair of blocks adds at most 32 to at most 15 pending
-  static_assert(CAP == 64 || CAP == 48, "pending capacity");
+  static_assert((NA & (NA - 1)) == 0 && DA % 2 == 0 && NA >= DA + 4, "ring depths");
   constexpr int kT = COLS / 16;           // 16-column MFMA tiles per wave
   constexpr int kStage = 16 * COLS * 2;   // one item: 16 B rows x COLS fp16
-  // A-fragment buffer row: CAP entries + a dummy entry (index CAP) + pad; 136 / 104 B rows put
+  // A-fragment buffer row: CAP entries + a dummy entry (index CAP) + pad; 104-B rows put
   // the four row groups' writes in different banks
-  constexpr int kAbRow = CAP == 64 ? 136 : 104;
+  constexpr int kAbRow = 104;
   constexpr int kAbuf = MSK ? 0 : NA * 512;   // offset of the A-fragment buffer
   constexpr int kStg = kAbuf + 16 * kAbRow;  // offset of the item stages
   constexpr int kLds = kStg + P * kStage;
   static_assert(kLds >= COLS * 16 * 4, "column-major C tile fits");
-  static_assert(!CST || kLds >= 16 * (COLS + 4) * 4, "row-major C tile fits");
+  static_assert(kLds >= 16 * (COLS + 4) * 4, "row-major C tile fits");
   __shared__ __attribute__((aligned(16))) char smem[kLds];
   const int lane = threadIdx.x;
   const int g = lane >> 4, r16 = lane & 15, h = lane >> 5;
@@ -2306,9 +2264,8 @@ __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
       const bool bit = (m[u] >> r16) & 1u;
       const int st = u ? s1 : s0;
       const int e = (st + __builtin_popcount(m[u] & lowm)) % CAP;
-      // inactive lanes: an entry the merge below does not take (CAP = 64: the one before
-      // the range; CAP = 48: lane 63, which holds no entry)
-      d[u] = 4 * (lane < 16 && bit ? e : (CAP == 64 ? (st + 63) & 63 : 63));
+      // inactive lanes: an entry the merge below does not take (lane 63, which holds none)
+      d[u] = 4 * (lane < 16 && bit ? e : 63);
       // A values of column r16, rows 4g .. 4g + 3 -> buffer column (entry CAP for empty columns)
       wa[u] = (int)(abuf + 2u * (unsigned)(bit ? e : CAP) + kAbRow * 4u * g);
     }
@@ -2356,47 +2313,41 @@ __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
       // the MFMAs, once its fragments are in registers, measured 2.5 % slower)
       if (kind[s]) {
         wait_vm_older(nis - stamp[s]);
+        static_assert(kT == 16, "the reads below are written out for 16 tiles");
+        f16x4 fb[16];
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %8 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %1, %9 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %2, %10 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %3, %11 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %4, %12 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %5, %13 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %6, %14 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %7, %15 offset:%16\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(fb[0]), "=&v"(fb[1]), "=&v"(fb[2]), "=&v"(fb[3]), "=&v"(fb[4]),
+              "=&v"(fb[5]), "=&v"(fb[6]), "=&v"(fb[7])
+            : "v"(tra[0]), "v"(tra[1]), "v"(tra[2]), "v"(tra[3]), "v"(tra[4]), "v"(tra[5]),
+              "v"(tra[6]), "v"(tra[7]), "n"(s * kStage)
+            : "memory");
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %8 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %1, %9 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %2, %10 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %3, %11 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %4, %12 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %5, %13 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %6, %14 offset:%16\n\t"
+            "ds_read_b64_tr_b16 %7, %15 offset:%16\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(fb[8]), "=&v"(fb[9]), "=&v"(fb[10]), "=&v"(fb[11]), "=&v"(fb[12]),
+              "=&v"(fb[13]), "=&v"(fb[14]), "=&v"(fb[15])
+            : "v"(tra[8]), "v"(tra[9]), "v"(tra[10]), "v"(tra[11]), "v"(tra[12]), "v"(tra[13]),
+              "v"(tra[14]), "v"(tra[15]), "n"(s * kStage)
+            : "memory");
 #pragma unroll
-        for (int hh = 0; hh < (kT + 15) / 16; ++hh) {
-          f16x4 fb[16];
-          asm volatile(
-              "ds_read_b64_tr_b16 %0, %8 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %1, %9 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %2, %10 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %3, %11 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %4, %12 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %5, %13 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %6, %14 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %7, %15 offset:%16\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(fb[0]), "=&v"(fb[1]), "=&v"(fb[2]), "=&v"(fb[3]), "=&v"(fb[4]),
-                "=&v"(fb[5]), "=&v"(fb[6]), "=&v"(fb[7])
-              : "v"(tra[16 * hh]), "v"(tra[16 * hh + 1]), "v"(tra[16 * hh + 2]),
-                "v"(tra[16 * hh + 3]), "v"(tra[16 * hh + 4]), "v"(tra[16 * hh + 5]),
-                "v"(tra[16 * hh + 6]), "v"(tra[16 * hh + 7]), "n"(s * kStage)
-              : "memory");
-          if constexpr (kT >= 16) asm volatile(
-              "ds_read_b64_tr_b16 %0, %8 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %1, %9 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %2, %10 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %3, %11 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %4, %12 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %5, %13 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %6, %14 offset:%16\n\t"
-              "ds_read_b64_tr_b16 %7, %15 offset:%16\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(fb[8]), "=&v"(fb[9]), "=&v"(fb[10]), "=&v"(fb[11]), "=&v"(fb[12]),
-                "=&v"(fb[13]), "=&v"(fb[14]), "=&v"(fb[15])
-              : "v"(tra[(16 * hh + 8) % kT]), "v"(tra[(16 * hh + 9) % kT]),
-                "v"(tra[(16 * hh + 10) % kT]), "v"(tra[(16 * hh + 11) % kT]),
-                "v"(tra[(16 * hh + 12) % kT]), "v"(tra[(16 * hh + 13) % kT]),
-                "v"(tra[(16 * hh + 14) % kT]), "v"(tra[(16 * hh + 15) % kT]), "n"(s * kStage)
-              : "memory");
-#pragma unroll
-          for (int t = 0; t < (kT < 16 ? kT : 16); ++t)
-            acc[16 * hh + t] =
-                __builtin_amdgcn_mfma_f32_16x16x16f16(fa[s], fb[t], acc[16 * hh + t], 0, 0, 0);
-        }
+        for (int t = 0; t < kT; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x16f16(fa[s], fb[t], acc[t], 0, 0, 0);
       }
       // produce the next item into slot s: read blocks until 16 columns are
       // pending or the blocks run out
@@ -2490,11 +2441,12 @@ __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
     }
     return;
   }
-  if constexpr (CST) {
+  {
     // row-major C through LDS: the 16 x COLS tile (row pitch COLS + 4 floats: the two
     // half-waves' rows in different banks), then each row as 64 lanes x 16 B (1 KB per
-    // store instruction; the register layout stores 4 x 64-B row pieces per instruction:
-    // products stand-in 3.91-4.04 -> 3.79-3.90 ms, profiles/r03_epilogue_ab.txt)
+    // store instruction; storing from the register layout, 4 x 64-B row pieces per
+    // instruction: products stand-in 3.91-4.04 -> 3.79-3.90 ms,
+    // profiles/r03_epilogue_ab.txt)
     constexpr int kTp = COLS + 4;
     float* tile = reinterpret_cast<float*>(smem);
 #pragma unroll
@@ -2503,8 +2455,8 @@ __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
       for (int e = 0; e < 4; ++e) tile[(4 * g + e) * kTp + 16 * t + r16] = acc[t][e];
     __builtin_amdgcn_s_waitcnt(0);
     const bool vec = (ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
-    constexpr int kLpr = COLS >= 256 ? 64 : COLS / 4;  // lanes per row piece
-    constexpr int kRpp = 64 / kLpr;                    // rows per store instruction
+    constexpr int kLpr = 64;         // lanes per row piece
+    constexpr int kRpp = 64 / kLpr;  // rows per store instruction
 #pragma unroll
     for (int cc = 0; cc < COLS; cc += 4 * kLpr) {
       const int col = jt + cc + 4 * (lane % kLpr);
@@ -2530,26 +2482,14 @@ __global__ __launch_bounds__(64) void bsr16_f16_cs_kernel(
         }
       }
     }
-    return;
-  }
-#pragma unroll
-  for (int t = 0; t < kT; ++t) {
-    const int j = jt + 16 * t + r16;
-    if (j >= n) continue;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const size_t row = (size_t)br * 16 + 4 * g + e;
-      float* p = C + row * ldc + j;
-      __builtin_nontemporal_store(epi(acc[t][e], alpha, beta, p), p);
-    }
   }
 }
 
 // ---------------------------------------------------------------------------
 // bs = 16 fp32 MFMA. Each wave: 16 rows x 64 columns (4 tiles of 16).
 // ---------------------------------------------------------------------------
-template <bool ROWDIR, bool BROW, bool CROW, int VAR>
-__global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f32_mfma_kernel(
+template <bool ROWDIR, bool BROW, bool CROW>
+__global__ __launch_bounds__(256, 1) void bsr16_f32_mfma_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const float* __restrict__ val, const float* __restrict__ B, int ldb, float alpha, float beta,
     float* __restrict__ C, int ldc) {
@@ -2576,7 +2516,7 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f32_mf
 
   ColCursor cc(colind, k0, k1, lane);
   auto load_frags = [&](int k, float (&fa)[4], float (&fb)[NT][4]) {
-    const int bc = (VAR & 4) != 0 ? colind[k] : cc.get(k);
+    const int bc = cc.get(k);
     const float* ab = val + (size_t)k * 256;
     if constexpr (ROWDIR) {
       const f32x4 x = *reinterpret_cast<const f32x4*>(ab + r * 16 + 4 * q);
@@ -2605,45 +2545,22 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f32_mf
       for (int t = 0; t < NT; ++t)
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[s], fb[t][s], acc[t], 0, 0, 0);
   };
-  float a0[4], b0[NT][4];
-  if constexpr ((VAR & 3) == 0) {
-    // Rotation prefetch: next block loaded under a branch, copied down after use.
-    float a1[4], b1[NT][4];
-    if (k0 < k1) {
+  // Rotation prefetch: next block loaded under a branch, copied down after use. (The
+  // load-use and fixed-role double-buffer pipelines: DESIGN.md §4 "Variant history".)
+  float a0[4], b0[NT][4], a1[4], b1[NT][4];
+  if (k0 < k1) {
     load_frags(k0, a0, b0);
     settle(a0);
     settle(b0);
   }
-    for (int k = k0; k < k1; ++k) {
-      if (k + 1 < k1) load_frags(k + 1, a1, b1);
-      mfma(a0, b0);
+  for (int k = k0; k < k1; ++k) {
+    if (k + 1 < k1) load_frags(k + 1, a1, b1);
+    mfma(a0, b0);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        a0[s] = a1[s];
+    for (int s = 0; s < 4; ++s) {
+      a0[s] = a1[s];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) b0[t][s] = b1[t][s];
-      }
-    }
-  } else if constexpr ((VAR & 3) == 2) {
-    // Load-use: latency hidden by occupancy alone (fewest VGPRs).
-    for (int k = k0; k < k1; ++k) {
-      load_frags(k, a0, b0);
-      mfma(a0, b0);
-    }
-  } else {
-    // Fixed-role double buffer, unconditional clamped prefetch (as bs = 32).
-    float a1[4], b1[NT][4];
-    const int kl = k1 - 1;
-    if (k0 < k1) {
-    load_frags(k0, a0, b0);
-    settle(a0);
-    settle(b0);
-  }
-    for (int k = k0; k < k1; k += 2) {
-      load_frags(min(k + 1, kl), a1, b1);
-      mfma(a0, b0);
-      load_frags(min(k + 2, kl), a0, b0);
-      if (k + 1 < k1) mfma(a1, b1);
+      for (int t = 0; t < NT; ++t) b0[t][s] = b1[t][s];
     }
   }
 
@@ -2664,8 +2581,8 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f32_mf
 // bs = 16 fp16 MFMA (v_mfma_f32_16x16x32_f16): two blocks per instruction.
 // Lane quad q: q < 2 -> block b, k = 8q + e; q >= 2 -> block b+1, k = 8(q-2) + e.
 // ---------------------------------------------------------------------------
-template <bool ROWDIR, bool BROW, bool CROW, int VAR>
-__global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f16_mfma_kernel(
+template <bool ROWDIR, bool BROW, bool CROW>
+__global__ __launch_bounds__(256, 1) void bsr16_f16_mfma_kernel(
     int mb, int n, const int* __restrict__ rowptr, const int* __restrict__ colind,
     const _Float16* __restrict__ val, const _Float16* __restrict__ B, int ldb, float alpha,
     float beta, float* __restrict__ C, int ldc) {
@@ -2692,22 +2609,18 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f16_mf
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // The block columns come by per-lane loads below; the readlane cursor of the other MFMA
+  // kernels lost here (DESIGN.md §4 "Variant history"). Its first fill is still issued: it
+  // is part of the shipped instruction stream, which this kernel keeps as measured.
   ColCursor cc(colind, k0, k1, lane);
-  // k: first block of the pair; kk = k + half is this lane's block. When the
+  (void)cc;
+  // k: first block of the pair; kl = k + half is this lane's block. When the
   // pair is incomplete the second half re-reads block k and is zeroed at use.
-  // k is clamped by the caller to <= k1 - 1; both cursor reads are
-  // unconditional (no branch around a load).
+  // k is clamped by the caller to <= k1 - 1.
   auto load_frags = [&](int k, f16x8& fa, f16x8 (&fb)[NT]) {
     const int k2 = min(k + 1, k1 - 1);
     const int kl = half ? k2 : k;
-    int bc;
-    if constexpr ((VAR & 4) != 0) {
-      bc = colind[kl];  // per-lane load (two addresses per wave)
-    } else {
-      const int bc0 = cc.get(k);
-      const int bc1 = cc.get(k2);
-      bc = half ? bc1 : bc0;
-    }
+    const int bc = colind[kl];  // per-lane load (two addresses per wave)
     const _Float16* ab = val + (size_t)kl * 256;
     if constexpr (ROWDIR) {
       fa = *reinterpret_cast<const f16x8*>(ab + r * 16 + kq);
@@ -2735,42 +2648,19 @@ __global__ __launch_bounds__(256, (VAR >> 3) ? (VAR >> 3) : 1) void bsr16_f16_mf
     for (int t = 0; t < NT; ++t)
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fz, fb[t], acc[t], 0, 0, 0);
   };
-  f16x8 a0, b0[NT];
-  if constexpr ((VAR & 3) == 0) {
-    // Rotation prefetch: next pair loaded under a branch, copied down after use.
-    f16x8 a1, b1[NT];
-    if (k0 < k1) {
+  // Rotation prefetch: next pair loaded under a branch, copied down after use.
+  f16x8 a0, b0[NT], a1, b1[NT];
+  if (k0 < k1) {
     load_frags(k0, a0, b0);
     settle(a0);
     settle(b0);
   }
-    for (int k = k0; k < k1; k += 2) {
-      if (k + 2 < k1) load_frags(k + 2, a1, b1);
-      mfma(a0, b0, k);
-      a0 = a1;
+  for (int k = k0; k < k1; k += 2) {
+    if (k + 2 < k1) load_frags(k + 2, a1, b1);
+    mfma(a0, b0, k);
+    a0 = a1;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) b0[t] = b1[t];
-    }
-  } else if constexpr ((VAR & 3) == 2) {
-    // Load-use over block pairs: latency hidden by occupancy alone.
-    for (int k = k0; k < k1; k += 2) {
-      load_frags(k, a0, b0);
-      mfma(a0, b0, k);
-    }
-  } else {
-    f16x8 a1, b1[NT];  // fixed-role double buffer over block pairs
-    const int kl = k1 - 1;
-    if (k0 < k1) {
-    load_frags(k0, a0, b0);
-    settle(a0);
-    settle(b0);
-  }
-    for (int k = k0; k < k1; k += 4) {
-      load_frags(min(k + 2, kl), a1, b1);
-      mfma(a0, b0, k);
-      load_frags(min(k + 4, kl), a0, b0);
-      if (k + 2 < k1) mfma(a1, b1, k + 2);
-    }
+    for (int t = 0; t < NT; ++t) b0[t] = b1[t];
   }
 
   const size_t row0 = (size_t)br * 16 + 4 * q;
@@ -3915,22 +3805,22 @@ void bsr32_f32_grp_kernel(
   }
 }
 
-// Fallback register-fragment kernels (layouts the copy kernels do not cover):
-// bsr32_f32_mfma_kernel / bsr16_*_mfma_kernel variant VAR (launch bounds and
-// prefetch form; the best of the round-1 sweep, DESIGN.md §4 "Variant history").
-constexpr int kBsr32Default = 40;
-constexpr int kBsr16Default = 8;      // fp32 bs 16
-constexpr int kBsr16F16Default = 12;  // fp16 bs 16
-
-// Shipped kernels of the ROW-block, row-major-B path, and the alternatives a
+// Layouts the copy kernels do not cover run on the register-fragment kernels
+// (bsr32_f32_mfma_kernel / bsr16_*_mfma_kernel), each in the one form that won the
+// round-1 sweep; they have no variant number.
+//
+// Kernels of the ROW-block, row-major-B path, and the alternatives a
 // TUNING build (make TUNING=1, -DSPMM_TUNING) lets SPMM_BSR_VARIANT select for
-// A/B timing. A release build compiles the override out (variant_override()
-// is the constant -1), so no environment setting can change which kernel
-// computes a product; the parity subset of each alternative is on record per
+// A/B timing. A release build compiles the override out (kTuning is false and
+// variant_override() the constant -1), so no environment setting can change
+// which kernel computes a product, and the alternatives' kernels are not
+// instantiated; the parity subset of each alternative is on record per
 // value in profiles/r04_var_tests/ (tools/gpu_var.sh, a TUNING build).
-// History of the removed variants: DESIGN.md §4.
-//  bs 32 fp32 (bsr32_f32_cs2_kernel: 6 item slots, 3 A slots, 32-bit B-row
-//  offsets, cross-block pairs, nt A copies): products stand-in 3.07 ms
+// The numbers are names only: the ring depths and forms they once encoded are
+// constants of the kernels now. History of the removed variants: DESIGN.md §4
+// "Variant history".
+//  bs 32 fp32 (bsr32_f32_cs2_kernel: 32-bit B-row offsets, nt A copies):
+//  products stand-in 3.07 ms
 //  against 3.15 without nt A (4516, round 2's default), reddit 1.93 / 2.04
 //  (profiles/r03_var_sweep.jsonl). 4496: the same without 32-bit offsets,
 //  for 32 * ldb * 4 >= 2^31. 4126, not selectable: the full-panel LDS kernel
@@ -3942,7 +3832,7 @@ constexpr int kBsr16F16Default = 12;  // fp16 bs 16
 constexpr int kBsr32Cs = 4416;
 constexpr int kBsr32CsNoNt = 4516;
 constexpr int kBsr32CsWideLdb = 4496;
-constexpr int kBsr32Dense = 4126;
+[[maybe_unused]] constexpr int kBsr32Dense = 4126;  // named in comments only
 //  bs 16 fp16, n >= 128 (bsr16_f16_cs_kernel: 2 item stages, 4 A slots, a
 //  48-entry pending list, whole-row copies, nt A copies; 19.7 KB of LDS, 8
 //  waves per CU), row-major C through an LDS tile (1-KB row stores): products
@@ -4138,7 +4028,7 @@ void launch_panel(const BsrArgs<float>& a, dim3 grid, int mbx, const int* ord,
       [&](auto cr, auto c64) {
         constexpr bool CR = decltype(cr)::value, C64 = decltype(c64)::value;
         SPMM_LAUNCH(a.ctx, 
-            (bsr32_f32_panel_kernel<CR, C64, C64 ? SPMM_PANEL_D64 : SPMM_PANEL_D128, SUB>), grid,
+            (bsr32_f32_panel_kernel<CR, C64, SUB>), grid,
             dim3(64), 0, mbx, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb, a.alpha,
             a.beta, a.C, a.ldc, ord, pstat);
       },
@@ -4154,7 +4044,7 @@ spmm_status_t bs32_dense_lds(const BsrArgs<float>& a, bool split) {
   spmm::with_bools(
       [&](auto cr, auto sp) {
         constexpr bool CR = decltype(cr)::value, SP = decltype(sp)::value;
-        SPMM_LAUNCH(a.ctx, (bsr32_f32_lds_kernel<CR, 2, 32, false, 24, SP, SP && CR>), grid,
+        SPMM_LAUNCH(a.ctx, (bsr32_f32_lds_kernel<CR, false, SP>), grid,
                     dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
                     a.ldb, a.alpha, a.beta, a.C, a.ldc, nullptr, nullptr, nullptr, 0,
                     nullptr);
@@ -4196,24 +4086,26 @@ spmm_status_t bs32_column_stream(const BsrArgs<float>& a, bool msk, int lv) {
         [&](auto cr, auto o32, auto c64_) {
           constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
                          C64 = decltype(c64_)::value;
-          SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, true, false, C64>),
+          SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, O32, true, true, false, C64>),
                       g2, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind, a.val,
                       a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt, a.masks);
         },
         a.crow, narrow, c64);
   } else {
-    // 32-bit offsets O32 and nt A copies ANT, by variant
+    // 32-bit offsets O32 and nt A copies ANT, by variant. Only a TUNING build has the
+    // kernels without nt A copies (no release build gets lv = kBsr32CsNoNt).
     auto stream = [&](auto o32, auto ant) {
-      spmm::with_bools(
-          [&](auto cr, auto c64_) {
-            constexpr bool CR = decltype(cr)::value, C64 = decltype(c64_)::value;
-            SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, decltype(o32)::value, true,
-                                              decltype(ant)::value, false, false, C64>),
-                        g2, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind,
-                        a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt,
-                        a.masks, pstat);
-          },
-          a.crow, c64);
+      if constexpr (decltype(ant)::value || spmm::kTuning)
+        spmm::with_bools(
+            [&](auto cr, auto c64_) {
+              constexpr bool CR = decltype(cr)::value, C64 = decltype(c64_)::value;
+              SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, decltype(o32)::value,
+                                                decltype(ant)::value, false, false, C64>),
+                          g2, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind,
+                          a.val, a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, sg, pt,
+                          a.masks, pstat);
+            },
+            a.crow, c64);
     };
     if (lv == kBsr32Cs) stream(std::true_type{}, std::true_type{});
     else if (lv == kBsr32CsNoNt) stream(std::true_type{}, std::false_type{});
@@ -4254,7 +4146,7 @@ spmm_status_t bs64_sub_stream(const BsrArgs<float>& a) {
       [&](auto cr, auto o32, auto c64) {  // c64: the 64-column tile
         constexpr bool CR = decltype(cr)::value, O32 = decltype(o32)::value,
                        C64 = decltype(c64)::value;
-        SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, 32, 6, 3, O32, true, true, false, true, C64>),
+        SPMM_LAUNCH(ctx, (bsr32_f32_cs2_kernel<CR, O32, true, false, true, C64>),
                     g2, dim3(64), 0, mb2, a.n, a.rowptr, a.colind, a.val, a.B,
                     a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, nullptr, nullptr, nullptr,
                     pstat);
@@ -4276,15 +4168,15 @@ spmm_status_t fragment_fallback(const BsrArgs<T>& a) {
         constexpr bool RD = decltype(rd)::value, BR = decltype(br)::value,
                        CR = decltype(cr)::value;
         if constexpr (std::is_same_v<T, _Float16>)
-          SPMM_LAUNCH(a.ctx, (bsr16_f16_mfma_kernel<RD, BR, CR, kBsr16F16Default>), grid, block, 0,
+          SPMM_LAUNCH(a.ctx, (bsr16_f16_mfma_kernel<RD, BR, CR>), grid, block, 0,
                       a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
                       a.alpha, a.beta, a.C, a.ldc);
         else if (a.bs == 32)
-          SPMM_LAUNCH(a.ctx, (bsr32_f32_mfma_kernel<RD, BR, CR, kBsr32Default>), grid, block, 0,
+          SPMM_LAUNCH(a.ctx, (bsr32_f32_mfma_kernel<RD, BR, CR>), grid, block, 0,
                       a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
                       a.alpha, a.beta, a.C, a.ldc);
         else
-          SPMM_LAUNCH(a.ctx, (bsr16_f32_mfma_kernel<RD, BR, CR, kBsr16Default>), grid, block, 0,
+          SPMM_LAUNCH(a.ctx, (bsr16_f32_mfma_kernel<RD, BR, CR>), grid, block, 0,
                       a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
                       a.alpha, a.beta, a.C, a.ldc);
       },
@@ -4302,7 +4194,7 @@ spmm_status_t bs16_column_masked(const BsrArgs<float>& a) {
     spmm::with_bools(
         [&](auto cr) {
           SPMM_LAUNCH(a.ctx, 
-              (bsr16_cm_kernel<float, decltype(cr)::value, 2, 5, 1, decltype(co)::value>), grid,
+              (bsr16_cm_kernel<float, decltype(cr)::value, decltype(co)::value>), grid,
               dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B, a.ldb,
               a.alpha, a.beta, a.C, a.ldc);
         },
@@ -4413,7 +4305,7 @@ spmm_status_t bs16_f16_column_masked(const BsrArgs<_Float16>& a) {
   const dim3 grid(a.mb, (a.n + 255) / 256);
   spmm::with_bools(
       [&](auto cr) {
-        SPMM_LAUNCH(a.ctx, (bsr16_cm_kernel<_Float16, decltype(cr)::value, 2, 5, 8>), grid,
+        SPMM_LAUNCH(a.ctx, (bsr16_cm_kernel<_Float16, decltype(cr)::value, 256>), grid,
                     dim3(256), 0, a.mb, a.n, a.rowptr, a.colind, a.val, a.B,
                     a.ldb, a.alpha, a.beta, a.C, a.ldc);
       },
@@ -4430,16 +4322,18 @@ spmm_status_t bs16_f16_column_stream(const BsrArgs<_Float16>& a, bool msk, int l
   if (spmm_status_t st = block_row_order(ctx, a.mb, gc.y, a.rowptr, &ord)) return st;
   const int ntt = tuning_env_int("SPMM_CS16_TT", 0) && gc.y > 1 ? (int)gc.y : 0;
   const dim3 gg = ntt ? dim3((unsigned)(8 * ((a.mb + 7) / 8) * ntt), 1) : gc;
+  // only a TUNING build has the kernels without nt A copies (no release build gets
+  // lv = kBsr16F16CsNoNt)
   auto stream = [&](auto ant, auto mk) {
-    spmm::with_bools(
-        [&](auto cr) {
-          SPMM_LAUNCH(ctx, (bsr16_f16_cs_kernel<decltype(cr)::value, 2, 4, 0, 48,
-                                           decltype(ant)::value, true, 256,
-                                           decltype(mk)::value>),
-                      gg, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind, a.val,
-                      a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, a.masks, ntt);
-        },
-        a.crow);
+    if constexpr (decltype(ant)::value || spmm::kTuning)
+      spmm::with_bools(
+          [&](auto cr) {
+            SPMM_LAUNCH(ctx, (bsr16_f16_cs_kernel<decltype(cr)::value, decltype(ant)::value,
+                                             decltype(mk)::value>),
+                        gg, dim3(64), 0, a.mb, a.n, a.rowptr, a.colind, a.val,
+                        a.B, a.ldb, a.alpha, a.beta, a.C, a.ldc, ord, a.masks, ntt);
+          },
+          a.crow);
   };
   if (msk) stream(std::true_type{}, std::true_type{});
   else if (lv == kBsr16F16Cs) stream(std::true_type{}, std::false_type{});
@@ -4562,7 +4456,7 @@ spmm_status_t launch_hybrid32_fused(spmm_context* ctx, int m, int n, float alpha
     with_bools(
         [&](auto sp) {
           constexpr bool SP = decltype(sp)::value;
-          SPMM_LAUNCH(ctx, (bsr32_f32_lds_kernel<true, 2, 32, true, 24, SP, SP>), grid, dim3(256),
+          SPMM_LAUNCH(ctx, (bsr32_f32_lds_kernel<true, true, SP>), grid, dim3(256),
                       0, mb, n, brp, bci, bval, B, ldb, alpha, beta, C, ldc,
                       crp, cci, cv, m, ord);
         },

@@ -1235,7 +1235,9 @@ spmm_status_t launch_csrmm_rowmajor(spmm_context* ctx, int m, int n, const int* 
     // lanes per nnz: 4 columns each, so 2 / 4 / 8 / 16 lanes cover K <= 8 / 16 / 32 / 64
     const int lanes = n <= 8 ? 2 : (n <= 16 ? 4 : (n <= 32 ? 8 : 16));
     with_int<2, 4, 8, 16>(lanes, [&](auto l) {
-      with_int<1, 4, 2>(pd == 1 || pd == 4 ? pd : 2, [&](auto d) {
+      // without an override pd follows from the lanes: 1 at 2 / 4, 2 at 8, 4 at 16
+      constexpr int L = decltype(l)::value;
+      with_tuned_int<(L <= 4 ? 1 : L / 4), 1, 4, 2>(pd == 1 || pd == 4 ? pd : 2, [&](auto d) {
         auto go = [&](auto nt_, auto hot_) {
           SPMM_LAUNCH(ctx, (csr_group_kernel<decltype(nt_)::value, decltype(l)::value,
                                         decltype(d)::value, decltype(hot_)::value>),

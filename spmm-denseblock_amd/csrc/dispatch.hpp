@@ -27,7 +27,15 @@ bool with_int(int v, F&& f) {
   return ((v == V ? (f(std::integral_constant<int, V>{}), true) : false) || ...);
 }
 
-// An integer a TUNING build (make TUNING=1) reads from the environment, once per use site.
+// A TUNING build (make TUNING=1)? `if constexpr (kTuning)` keeps the kernels only an
+// override can reach out of a release library.
+#ifdef SPMM_TUNING
+constexpr bool kTuning = true;
+#else
+constexpr bool kTuning = false;
+#endif
+
+// An integer a TUNING build reads from the environment, once per use site.
 // A release build compiles the name out: no environment setting changes a product there
 // (tests/test_abi.py looks for the names in the library).
 #ifdef SPMM_TUNING
@@ -42,6 +50,15 @@ bool with_int(int v, F&& f) {
 #else
 #define tuning_env_int(NAME, DFLT) (DFLT)
 #endif
+
+// f(std::integral_constant<int, D>{}), D the value a release build derives at compile
+// time. A TUNING build, where an override may have replaced it, takes v among V... at run
+// time instead (with_int), so only that build instantiates f for every V.
+template <int D, int... V, typename F>
+void with_tuned_int(int v, F&& f) {
+  if constexpr (kTuning) with_int<V...>(v, f);
+  else f(std::integral_constant<int, D>{});
+}
 
 // The timing pair around a launcher's body, closed on every path. A body that fails
 // returns its own status; else the launches' error, read after the stop event is recorded.

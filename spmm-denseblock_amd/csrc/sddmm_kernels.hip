@@ -270,9 +270,12 @@ Picked picked() {
 
 template <int G, int NC>
 Picked pick(bool vec, bool full) {
-  if (vec)
-    return full ? picked<sddmm_kernel<G, NC, true, true>>()
-                : picked<sddmm_kernel<G, NC, true, false>>();
+  if (vec) {
+    // G = 1 / 2 (n <= 8): the only n with n % 4 == 0 is 4 G itself, so vec implies full
+    if constexpr (G > 2)
+      if (!full) return picked<sddmm_kernel<G, NC, true, false>>();
+    return picked<sddmm_kernel<G, NC, true, true>>();
+  }
   return full ? picked<sddmm_kernel<G, NC, false, true>>()
               : picked<sddmm_kernel<G, NC, false, false>>();
 }

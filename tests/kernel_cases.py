@@ -79,13 +79,10 @@ class Case:
 
 # Kernels of the five files outside the dispatch trace that no argument tuple of a release
 # build reaches: (pattern, how many, the launcher lines that prove it).
-UNREACHABLE_OTHER = [
-    # launch_sddmm (sddmm_kernels.hip): G = group_lanes(n) is the smallest power of two >=
-    # ceil(n / 4); vec needs n % 4 == 0 and full is n % (4 G) == 0. At G = 1 (n <= 4) and
-    # G = 2 (5 <= n <= 8) the only n with n % 4 == 0 is 4 G itself, so vec implies full and
-    # pick<G, 1>(true, false) is never asked for.
-    (r"12sddmm_kernelILi[12]ELi1ELb1ELb0EE", 2, "vec implies full at G = 1 / 2"),
-]
+# Empty today. (launch_sddmm no longer instantiates sddmm_kernel<G, 1, vec, !full> at
+# G = 1 / 2: G = group_lanes(n) is the smallest power of two >= ceil(n / 4), vec needs
+# n % 4 == 0 and full is n % (4 G) == 0, and the only such n at G = 1 / 2 is 4 G itself.)
+UNREACHABLE_OTHER: list[tuple[str, int, str]] = []
 
 
 # ------------------------------------------------------------------ BSR matrices
@@ -1002,129 +999,129 @@ TRACED_CASES = [
     Case("bsrmm-bs32-n64-row-br-cr-wide", "bsrmm",
          B(shape='wide', bs=32, n=64),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb0ELb0ELb1EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm_analysed-bs32-n64-col-br-cr-wide", "bsrmm_analysed",
          B(rowd=0, shape='wide', bs=32, n=64),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb1ELb0ELb1EEEviiPKi",
           "16seg_fixup_kernelEiPK",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm-bs32-n132-row-br-cr-wide", "bsrmm",
          B(shape='wide', bs=32, n=132),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb0ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cr-wide", "bsrmm_analysed",
          B(rowd=0, shape='wide', bs=32, n=132),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb1ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm-bs32-n64-row-br-cc-wide", "bsrmm",
          B(oc=1, shape='wide', bs=32, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm_analysed-bs32-n64-col-br-cc-wide", "bsrmm_analysed",
          B(rowd=0, oc=1, shape='wide', bs=32, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb1ELb0ELb1EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm-bs32-n132-row-br-cc-wide", "bsrmm",
          B(oc=1, shape='wide', bs=32, n=132),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cc-wide", "bsrmm_analysed",
          B(rowd=0, oc=1, shape='wide', bs=32, n=132),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb1ELb0ELb0EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm-bs64-n64-row-br-cr-wide", "bsrmm",
          B(shape='wide', bs=64, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n132-row-br-cr-wide", "bsrmm",
          B(shape='wide', bs=64, n=132),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb0ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs64-n64-row-br-cc-wide", "bsrmm",
          B(oc=1, shape='wide', bs=64, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n132-row-br-cc-wide", "bsrmm",
          B(oc=1, shape='wide', bs=64, n=132),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb0ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n8-row-br-cr-panel", "bsrmm",
          B(shape='panel', bs=32, n=8),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm-bs32-n68-row-br-cr-panel", "bsrmm",
          B(shape='panel', bs=32, n=68),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm-bs32-n8-row-br-cc-panel", "bsrmm",
          B(oc=1, shape='panel', bs=32, n=8),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb0ELb1ELi2ELb0EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb0ELb1ELb0EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n68-row-br-cc-panel", "bsrmm",
          B(oc=1, shape='panel', bs=32, n=68),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb0ELb0ELi2ELb0EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb0ELb0ELb0EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs64-n8-row-br-cr-panel", "bsrmm",
          B(shape='panel', bs=64, n=8),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb1ELb1ELi2ELb1EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb1ELb1ELb1EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n68-row-br-cr-panel", "bsrmm",
          B(shape='panel', bs=64, n=68),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb1ELb0ELi2ELb1EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb1ELb0ELb1EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs64-n8-row-br-cc-panel", "bsrmm",
          B(oc=1, shape='panel', bs=64, n=8),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb0ELb1ELi2ELb1EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb1EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb0ELb1ELb1EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n68-row-br-cc-panel", "bsrmm",
          B(oc=1, shape='panel', bs=64, n=68),
          ("22block_row_order_kernelEiPKi",
           "18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb0ELb0ELi2ELb1EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb0ELb0ELb1EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n8-row-br-cr-deep-panel", "bsrmm",
          B(shape='deep-panel', bs=32, n=8),
          ("18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb1ELb1ELi2ELb0EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb1ELb1ELb0EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n68-row-br-cr-deep-panel", "bsrmm",
          B(shape='deep-panel', bs=32, n=68),
          ("18panel_probe_kernelExiiPKfPy",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
-          "22bsr32_f32_panel_kernelILb1ELb0ELi2ELb0EEEviiPKi",),
-         idle=("20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
+          "22bsr32_f32_panel_kernelILb1ELb0ELb0EEEviiPKi",),
+         idle=("20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n8-row-br-cr-deep", "bsrmm",
          B(shape='deep', bs=32, n=8),
-         ("20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
+         ("20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n4-row-br-cc-deep", "bsrmm",
          B(oc=1, shape='deep', bs=64, n=4),
-         ("20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+         ("20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs8-n4-row-br-cr-deep-flags2", "bsrmm",
          B(shape='deep', bsr_flags=2, bs=8, n=4, small_path=2),
          ("22block_row_order_kernelEiPKi",
@@ -1135,21 +1132,21 @@ TRACED_CASES = [
     Case("bsrmm-bs32-n64-row-br-cr-boff4-coff4-padb4-padc4", "bsrmm",
          B(boff=4, coff=4, pad_b=4, pad_c=4, bs=32, n=64),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm-bs32-n64-row-br-cr-voff1", "bsrmm",
          B(voff=1, bs=32, n=64),
          ("18bsr_generic_kernelIfEEviiibPKi",)),
     Case("bsrmm-bs32-n64-row-br-cr-coff1-padc1", "bsrmm",
          B(coff=1, pad_c=1, bs=32, n=64),
-         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n64-row-br-cr-boff1-padb1", "bsrmm",
          B(boff=1, pad_b=1, bs=32, n=64),
-         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n132-row-br-cr-boff4-coff4-padb4-padc4", "bsrmm",
          B(boff=4, coff=4, pad_b=4, pad_c=4, bs=64, n=132),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs64-n132-row-br-cr-voff1", "bsrmm",
          B(voff=1, bs=64, n=132),
          ("18bsr_generic_kernelIfEEviiibPKi",)),
@@ -1161,16 +1158,16 @@ TRACED_CASES = [
          ("18bsr_generic_kernelIfEEviiibPKi",)),
     Case("bsrmm-bs16-n64-row-br-cr-boff4-coff4-padb4-padc4", "bsrmm",
          B(boff=4, coff=4, pad_b=4, pad_c=4, bs=16, n=64),
-         ("15bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi64EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb1ELi64EEEviiPKi",)),
     Case("bsrmm-bs16-n64-row-br-cr-voff1", "bsrmm",
          B(voff=1, bs=16, n=64),
          ("18bsr_generic_kernelIfEEviiibPKi",)),
     Case("bsrmm-bs16-n64-row-br-cr-coff1-padc1", "bsrmm",
          B(coff=1, pad_c=1, bs=16, n=64),
-         ("15bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi64EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb1ELi64EEEviiPKi",)),
     Case("bsrmm-bs16-n64-row-br-cr-boff1-padb1", "bsrmm",
          B(boff=1, pad_b=1, bs=16, n=64),
-         ("21bsr16_f32_mfma_kernelILb1ELb1ELb1ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb1ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs8-n132-row-br-cr-boff4-coff4-padb4-padc4", "bsrmm",
          B(boff=4, coff=4, pad_b=4, pad_c=4, bs=8, n=132),
          ("16bsr_small_kernelILi8ELi2ELb1ELb1EEEviiPKi",)),
@@ -1186,58 +1183,58 @@ TRACED_CASES = [
     Case("bsrmm_f16-bs16-n136-row-br-cr-boff8-coff4-padb8-padc4", "bsrmm_f16",
          B(boff=8, coff=4, pad_b=8, pad_c=4, bs=16, n=136),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb1ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb0EEEviiPKi",)),
+          "19bsr16_f16_cs_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n136-row-br-cr-voff1", "bsrmm_f16",
          B(voff=1, bs=16, n=136),
          ("18bsr_generic_kernelIDF16_EEviiibPKi",)),
     Case("bsrmm_f16-bs16-n136-row-br-cr-coff1-padc1", "bsrmm_f16",
          B(coff=1, pad_c=1, bs=16, n=136),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb1ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb0EEEviiPKi",)),
+          "19bsr16_f16_cs_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n136-row-br-cr-boff1-padb1", "bsrmm_f16",
          B(boff=1, pad_b=1, bs=16, n=136),
-         ("21bsr16_f16_mfma_kernelILb1ELb1ELb1ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb1ELb1ELb1EEEviiPKi",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cr-boff4-coff4-padb4-padc4", "bsrmm_analysed",
          B(rowd=0, boff=4, coff=4, pad_b=4, pad_c=4, bs=32, n=132),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cr-coff1-padc1", "bsrmm_analysed",
          B(rowd=0, coff=1, pad_c=1, bs=32, n=132),
-         ("21bsr32_f32_mfma_kernelILb0ELb1ELb1ELi40EEEviiPKi",
+         ("21bsr32_f32_mfma_kernelILb0ELb1ELb1EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cr-boff1-padb1", "bsrmm_analysed",
          B(rowd=0, boff=1, pad_b=1, bs=32, n=132),
-         ("21bsr32_f32_mfma_kernelILb0ELb1ELb1ELi40EEEviiPKi",
+         ("21bsr32_f32_mfma_kernelILb0ELb1ELb1EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("hybrid-bs32-n64-br-cr-lay4444", "hybrid_csrmm",
          H(boff=4, coff=4, pad_b=4, pad_c=4, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_lds_kernelILb1ELi2ELi32ELb1ELi24ELb0ELb0EEEviiPKi",)),
+          "20bsr32_f32_lds_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("hybrid-bs32-n64-br-cr-lay1113", "hybrid_csrmm",
          H(boff=1, coff=1, pad_b=1, pad_c=3, n=64),
-         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1ELi40EEEviiPKi",
+         ("21bsr32_f32_mfma_kernelILb1ELb1ELb1EEEviiPKi",
           "5CsrMpIfE20csr_mergepath_kernelILi1ELb1ELi0EEEviiPKi",)),
     Case("bsrmm-bs32-n132-row-br-cr-long", "bsrmm",
          B(shape='long', bs=32, n=132),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",)),
     Case("bsrmm_analysed-bs32-n132-col-br-cr-long", "bsrmm_analysed",
          B(rowd=0, shape='long', bs=32, n=132),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
           "16seg_fixup_kernelEiPK",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_f16-bs16-n136-row-br-cr-long", "bsrmm_f16",
          B(shape='long', bs=16, n=136),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb1ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb0EEEviiPKi",)),
+          "19bsr16_f16_cs_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_analysed_f16-bs16-n136-col-br-cr-long", "bsrmm_analysed_f16",
          B(rowd=0, shape='long', bs=16, n=136),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb1ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb1EEEviiPKi",
+          "19bsr16_f16_cs_kernelILb1ELb1ELb1EEEviiPKi",
           "21bsr16_analysis_kernelEiiPKtPjPt",)),
     Case("csrmm_hot-n68-bc-cr", "csrmm_hot",
          Cs(ob=1, n=68),
@@ -1249,16 +1246,16 @@ TRACED_CASES = [
           "17transpose4_kernelILb0EEEviiPKfiPfifj",)),
     Case("bsrmm_f16-bs16-n64-row-bc-cr", "bsrmm_f16",
          B(ob=1, bs=16, n=64),
-         ("15bsr16_cm_kernelIDF16_Lb1ELi2ELi5ELi8ELi256EEEviiPKi",
+         ("15bsr16_cm_kernelIDF16_Lb1ELi256EEEviiPKi",
           "20transpose16x4_kernelILb0EEEviiPKtiPtij",)),
     Case("hybrid-bs32-n64-bc-cc-flags0", "hybrid_csrmm",
          H(ob=1, oc=1, n=64),
-         ("20bsr32_f32_lds_kernelILb0ELi2ELi32ELb0ELi24ELb0ELb0EEEviiPKi",
+         ("20bsr32_f32_lds_kernelILb0ELb0ELb0EEEviiPKi",
           "16csr_group_kernelILb1ELi16ELi4ELb0EEEviiPKi",
           "17transpose4_kernelILb0EEEviiPKfiPfifj",)),
     Case("hybrid-bs32-n136-bc-cc-flags5", "hybrid_csrmm",
          H(ob=1, oc=1, hybrid_flags=5, n=136),
-         ("20bsr32_f32_lds_kernelILb0ELi2ELi32ELb0ELi24ELb1ELb0EEEviiPKi",
+         ("20bsr32_f32_lds_kernelILb0ELb0ELb1EEEviiPKi",
           "5CsrMpIfE20csr_mergepath_kernelILi4ELb1ELi0EEEviiPKi",
           "17transpose4_kernelILb0EEEviiPKfiPfifj",)),
     Case("bsrmm-bs2-n64-row-br-cr-shared-flags2", "bsrmm",
@@ -1364,134 +1361,134 @@ TRACED_CASES = [
          ("16bsr_small_kernelILi8ELi2ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs16-n68-row-br-cr", "bsrmm",
          B(bs=16, n=68),
-         ("15bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi128EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb1ELi128EEEviiPKi",)),
     Case("bsrmm-bs16-n132-row-br-cr", "bsrmm",
          B(bs=16, n=132),
-         ("15bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi256EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb1ELi256EEEviiPKi",)),
     Case("bsrmm-bs16-n4-row-br-cc", "bsrmm",
          B(oc=1, bs=16, n=4),
-         ("15bsr16_cm_kernelIfLb0ELi2ELi5ELi1ELi64EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb0ELi64EEEviiPKi",)),
     Case("bsrmm-bs16-n30-row-br-cc", "bsrmm",
          B(oc=1, bs=16, n=30),
-         ("21bsr16_f32_mfma_kernelILb1ELb1ELb0ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs16-n68-row-br-cc", "bsrmm",
          B(oc=1, bs=16, n=68),
-         ("15bsr16_cm_kernelIfLb0ELi2ELi5ELi1ELi128EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb0ELi128EEEviiPKi",)),
     Case("bsrmm-bs16-n132-row-br-cc", "bsrmm",
          B(oc=1, bs=16, n=132),
-         ("15bsr16_cm_kernelIfLb0ELi2ELi5ELi1ELi256EEEviiPKi",)),
+         ("15bsr16_cm_kernelIfLb0ELi256EEEviiPKi",)),
     Case("bsrmm-bs16-n30-row-bc-cr", "bsrmm",
          B(ob=1, bs=16, n=30),
-         ("21bsr16_f32_mfma_kernelILb1ELb0ELb1ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb1ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs16-n30-row-bc-cc", "bsrmm",
          B(ob=1, oc=1, bs=16, n=30),
-         ("21bsr16_f32_mfma_kernelILb1ELb0ELb0ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb1ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs16-n4-col-br-cr", "bsrmm",
          B(rowd=0, bs=16, n=4),
-         ("21bsr16_f32_mfma_kernelILb0ELb1ELb1ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs16-n4-col-br-cc", "bsrmm",
          B(rowd=0, oc=1, bs=16, n=4),
-         ("21bsr16_f32_mfma_kernelILb0ELb1ELb0ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs16-n4-col-bc-cr", "bsrmm",
          B(rowd=0, ob=1, bs=16, n=4),
-         ("21bsr16_f32_mfma_kernelILb0ELb0ELb1ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs16-n4-col-bc-cc", "bsrmm",
          B(rowd=0, ob=1, oc=1, bs=16, n=4),
-         ("21bsr16_f32_mfma_kernelILb0ELb0ELb0ELi8EEEviiPKi",)),
+         ("21bsr16_f32_mfma_kernelILb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n4-row-br-cc", "bsrmm",
          B(oc=1, bs=32, n=4),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n30-row-br-cc", "bsrmm",
          B(oc=1, bs=32, n=30),
-         ("21bsr32_f32_mfma_kernelILb1ELb1ELb0ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n68-row-br-cc", "bsrmm",
          B(oc=1, bs=32, n=68),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n30-row-bc-cr", "bsrmm",
          B(ob=1, bs=32, n=30),
-         ("21bsr32_f32_mfma_kernelILb1ELb0ELb1ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb1ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n30-row-bc-cc", "bsrmm",
          B(ob=1, oc=1, bs=32, n=30),
-         ("21bsr32_f32_mfma_kernelILb1ELb0ELb0ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb1ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n4-col-br-cc", "bsrmm",
          B(rowd=0, oc=1, bs=32, n=4),
-         ("21bsr32_f32_mfma_kernelILb0ELb1ELb0ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm-bs32-n4-col-bc-cr", "bsrmm",
          B(rowd=0, ob=1, bs=32, n=4),
-         ("21bsr32_f32_mfma_kernelILb0ELb0ELb1ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm-bs32-n4-col-bc-cc", "bsrmm",
          B(rowd=0, ob=1, oc=1, bs=32, n=4),
-         ("21bsr32_f32_mfma_kernelILb0ELb0ELb0ELi40EEEviiPKi",)),
+         ("21bsr32_f32_mfma_kernelILb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm-bs64-n4-row-br-cr", "bsrmm",
          B(bs=64, n=4),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm-bs64-n68-row-br-cc", "bsrmm",
          B(oc=1, bs=64, n=68),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-row-br-cc", "bsrmm_f16",
          B(oc=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb1ELb1ELb0ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb1ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n64-row-br-cc", "bsrmm_f16",
          B(oc=1, bs=16, n=64),
-         ("15bsr16_cm_kernelIDF16_Lb0ELi2ELi5ELi8ELi256EEEviiPKi",)),
+         ("15bsr16_cm_kernelIDF16_Lb0ELi256EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n128-row-br-cc", "bsrmm_f16",
          B(oc=1, bs=16, n=128),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb0ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb0EEEviiPKi",)),
+          "19bsr16_f16_cs_kernelILb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-row-bc-cr", "bsrmm_f16",
          B(ob=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb1ELb0ELb1ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb1ELb0ELb1EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-row-bc-cc", "bsrmm_f16",
          B(ob=1, oc=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb1ELb0ELb0ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb1ELb0ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-col-br-cr", "bsrmm_f16",
          B(rowd=0, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb0ELb1ELb1ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb0ELb1ELb1EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-col-br-cc", "bsrmm_f16",
          B(rowd=0, oc=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb0ELb1ELb0ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb0ELb1ELb0EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-col-bc-cr", "bsrmm_f16",
          B(rowd=0, ob=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb0ELb0ELb1ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb0ELb0ELb1EEEviiPKi",)),
     Case("bsrmm_f16-bs16-n4-col-bc-cc", "bsrmm_f16",
          B(rowd=0, ob=1, oc=1, bs=16, n=4),
-         ("21bsr16_f16_mfma_kernelILb0ELb0ELb0ELi12EEEviiPKi",)),
+         ("21bsr16_f16_mfma_kernelILb0ELb0ELb0EEEviiPKi",)),
     Case("bsrmm_analysed-bs32-n4-col-br-cr", "bsrmm_analysed",
          B(rowd=0, bs=32, n=4),
          ("16seg_build_kernelEiPKiiiiiiP",
-          "20bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb1ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb1ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
           "16seg_fixup_kernelEiPK",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_analysed-bs32-n4-col-br-cc", "bsrmm_analysed",
          B(rowd=0, oc=1, bs=32, n=4),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb1ELb0ELb1EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_analysed-bs32-n68-col-br-cc", "bsrmm_analysed",
          B(rowd=0, oc=1, bs=32, n=68),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_cs2_kernelILb0ELi32ELi6ELi3ELb1ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
+          "20bsr32_f32_cs2_kernelILb0ELb1ELb1ELb1ELb0ELb0EEEviiPKi",
           "21bsr32_analysis_kernelEiiPKfPjPf",)),
     Case("bsrmm_analysed_f16-bs16-n128-col-br-cc", "bsrmm_analysed_f16",
          B(rowd=0, oc=1, bs=16, n=128),
          ("22block_row_order_kernelEiPKi",
-          "19bsr16_f16_cs_kernelILb0ELi2ELi4ELi0ELi48ELb1ELb1ELi256ELb1EEEviiPKi",
+          "19bsr16_f16_cs_kernelILb0ELb1ELb1EEEviiPKi",
           "21bsr16_analysis_kernelEiiPKtPjPt",)),
     Case("hybrid-bs32-n64-br-cr-flags5", "hybrid_csrmm",
          H(hybrid_flags=5, n=64),
          ("22block_row_order_kernelEiPKi",
-          "20bsr32_f32_lds_kernelILb1ELi2ELi32ELb1ELi24ELb1ELb1EEEviiPKi",)),
+          "20bsr32_f32_lds_kernelILb1ELb1ELb1EEEviiPKi",)),
     Case("hybrid-bs32-n64-br-cr-flags2", "hybrid_csrmm",
          H(hybrid_flags=2, n=64),
-         ("20bsr32_f32_lds_kernelILb1ELi2ELi32ELb0ELi24ELb0ELb0EEEviiPKi",
+         ("20bsr32_f32_lds_kernelILb1ELb0ELb0EEEviiPKi",
           "16csr_group_kernelILb1ELi16ELi4ELb0EEEviiPKi",)),
     Case("hybrid-bs32-n64-br-cr-flags6", "hybrid_csrmm",
          H(hybrid_flags=6, n=64),
-         ("20bsr32_f32_lds_kernelILb1ELi2ELi32ELb0ELi24ELb1ELb1EEEviiPKi",
+         ("20bsr32_f32_lds_kernelILb1ELb0ELb1EEEviiPKi",
           "16csr_group_kernelILb1ELi16ELi4ELb0EEEviiPKi",)),
     Case("csrmm-n4-flags1-boff0-coff0-padb0-padc0", "csrmm",
          Cs(n=4),

@@ -26,20 +26,10 @@ def asm_path(name: str) -> str:
 # Kernels that ship but that no argument tuple of a release build reaches: (pattern over
 # the kernel's name and template arguments, how many it names, the condition that keeps
 # them out). Findings for a later change; nothing is dropped from the check silently.
-UNREACHABLE = [
-    # csr_group_kernel<NT, L, PD, HOT>: the launcher instantiates PD 1 / 2 / 4 at every L,
-    # for a TUNING build's SPMM_CSR_GROUP_PD; a release build derives both from n
-    # (n <= 16: L 2 / 4 with PD 1; n <= 32: L 8 with PD 2; else L 16 with PD 4)
-    (r"16csr_group_kernelILb[01]ELi[24]ELi[24]ELb[01]EE", 12, "L 2 / 4 with PD 2 / 4"),
-    (r"16csr_group_kernelILb[01]ELi8ELi[14]ELb[01]EE", 6, "L 8 with PD 1 / 4"),
-    (r"16csr_group_kernelILb[01]ELi16ELi[12]ELb[01]EE", 6, "L 16 with PD 1 / 2"),
-    # the column streams without nt A copies: SPMM_BSR_VARIANT 4516 / 6104, a TUNING
-    # build's override (variant_override() is the constant -1 in a release build)
-    (r"20bsr32_f32_cs2_kernelILb[01]ELi32ELi6ELi3ELb1ELb1ELb0ELb0ELb0ELb[01]EE", 4,
-     "ANT = false: variant 4516 only"),
-    (r"19bsr16_f16_cs_kernelILb[01]ELi2ELi4ELi0ELi48ELb0ELb1ELi256ELb0EE", 2,
-     "ANT = false: variant 6104 only"),
-]
+# Empty today: the kernels only a TUNING build's overrides select (csr_group_kernel's L x PD
+# cross product for SPMM_CSR_GROUP_PD, the column streams without nt A copies for
+# SPMM_BSR_VARIANT 4516 / 6104) are instantiated in that build alone.
+UNREACHABLE: list[tuple[str, int, str]] = []
 
 
 def shipped_kernels(files=HIP_FILES) -> list[str]:

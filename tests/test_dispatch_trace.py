@@ -52,8 +52,8 @@ def test_kernel_key():
         "_ZN12_GLOBAL__N_114hot_tag_kernelE"
     assert kernel_key("_ZN12_GLOBAL__N_15CsrMpIDF16_E20csr_mergepath_kernelILi4ELb1ELi0EEEviiPKi") == \
         "_ZN12_GLOBAL__N_15CsrMpIDF16_E20csr_mergepath_kernelILi4ELb1ELi0EEE"
-    assert kernel_key("_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi64EEEviiPKi") == \
-        "_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi64EEE"
+    assert kernel_key("_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi64EEEviiPKi") == \
+        "_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi64EEE"
 
 
 def test_every_shipped_kernel_is_reached(trace):
@@ -67,7 +67,7 @@ def test_every_shipped_kernel_is_reached(trace):
     for p in ASM:
         with open(p) as f:
             kernels += re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", f.read(), re.M)
-    assert len(kernels) == len(set(kernels)) and len(kernels) >= 197, len(kernels)
+    assert len(kernels) == len(set(kernels)) and len(kernels) == 167, len(kernels)
     keys = {k: kernel_key(k) for k in kernels}
     assert len(set(keys.values())) == len(kernels), "two kernels share a name and arguments"
     reached = {k for k in kernels if keys[k] in blob}

@@ -44,9 +44,9 @@ def bsr_asm() -> str:
 
 # The LDS-DMA kernels the library ships (bsr_kernels.hip dispatch): every
 # instantiation of each family must be audited.
-SHIPPED_DMA = {"bsr32_f32_lds_kernel": 6, "bsr32_f32_cs2_kernel": 20, "bsr16_cm_kernel": 8,
+SHIPPED_DMA = {"bsr32_f32_lds_kernel": 6, "bsr32_f32_cs2_kernel": 16, "bsr16_cm_kernel": 8,
                "bsr16_f16_grp_kernel": 6, "bsr32_f32_grp_kernel": 2,
-               "bsr16_f16_cs_kernel": 6}
+               "bsr16_f16_cs_kernel": 4}
 
 
 def test_every_stage_handoff_wait(bsr_asm):
@@ -141,9 +141,9 @@ def test_column_stream_counts_only_its_copies(bsr_asm, kernel):
         body = funcs[k]
         assert not any(line.strip().startswith("scratch_") for _, line in body), f"{k}: spills"
         blocks = iv.build_cfg(body)
-        # the analysed bs 32 form (MSK, 8th template argument) copies nothing into LDS:
+        # the analysed bs 32 form (MSK, 4th template argument) copies nothing into LDS:
         # its loops are the ones with inline-asm loads
-        msk = re.search(r"cs2_kernelI(?:L[bi]\d+E){7}Lb1E", k) is not None
+        msk = re.search(r"cs2_kernelI(?:L[bi]\d+E){3}Lb1E", k) is not None
         loops = {b.header for b in blocks
                  if b.in_loop and any(iv.classify(mn, ops) == "dma" or
                                       (msk and iv.classify(mn, ops) == "load" and no in b.asm_lines)

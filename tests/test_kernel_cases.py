@@ -31,9 +31,9 @@ def keys():
 
 
 def test_keys_are_one_to_one_with_symbols(keys):
-    """285 kernels today: at least the 197 of csr_kernels / bsr_kernels and the 88 of the
-    other five files, each with a key of its own (two files define a col_count_kernel)."""
-    assert len(keys) >= 285
+    """253 kernels: the 167 of csr_kernels / bsr_kernels and the 86 of the other five
+    files, each with a key of its own (two files define a col_count_kernel)."""
+    assert len(keys) == 253
     assert sum("16col_count_kernelE" in k for k in keys) == 2
 
 
@@ -50,10 +50,11 @@ def test_every_pattern_names_a_shipped_kernel(keys):
 
 
 def test_unreachable_lists(keys):
-    """The lists hold what they say: the 30 TUNING-only kernels of the traced files
-    (tests/test_dispatch_trace.py checks that no trace tuple reaches them) and the kernels
-    of the other files that kernel_cases.UNREACHABLE_OTHER proves out of reach."""
-    assert sum(n for _, n, _ in UNREACHABLE) == 30
+    """The lists hold what they say (nothing today: TUNING-only kernels no longer ship):
+    kernels of the traced files that no trace tuple reaches (tests/test_dispatch_trace.py
+    checks that) and kernels of the other files that kernel_cases.UNREACHABLE_OTHER proves
+    out of reach."""
+    assert sum(n for _, n, _ in UNREACHABLE) == 0
     for pat, count, why in UNREACHABLE + kc.UNREACHABLE_OTHER:
         assert sum(bool(re.search(pat, k)) for k in keys) == count, why
 
@@ -114,8 +115,7 @@ def test_wide_ldb_cases_cover_the_64_bit_offset_streams(keys):
     """All 12 O32 = false instantiations of bsr32_f32_cs2_kernel (plain, analysed and SUB,
     each by CR x C64) are expected by a case with ldb = 2^24 whose blocks reach B rows past
     2^31 bytes."""
-    o32_false = {k for k in keys
-                 if re.search(r"20bsr32_f32_cs2_kernelILb[01]ELi32ELi6ELi3ELb0E", k)}
+    o32_false = {k for k in keys if re.search(r"20bsr32_f32_cs2_kernelILb[01]ELb0E", k)}
     assert len(o32_false) == 12
     seen = set()
     for c in kc.CASES:

@@ -65,3 +65,32 @@ def test_a_changed_descriptor_field_is_flagged():
 def test_a_missing_kernel_is_flagged():
     got = kid.compare(A, _kernel("_Z1aILb1EEvPf", 0))
     assert got == [("only in A", "_Z1aILb0EEvPf", "")]
+
+
+_OLD = "_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi2ELi5ELi1ELi64EEEviiPKiS2_PKT_S5_iffPfi"
+_NEW = "_ZN12_GLOBAL__N_115bsr16_cm_kernelIfLb1ELi64EEEviiPKiS2_PKT_S5_iffPfi"
+
+
+def test_a_dropped_template_parameter_renames_the_symbol():
+    assert kid.renamed(_OLD) == _NEW
+    assert kid.renamed("_ZN12_GLOBAL__N_120bsr32_f32_cs2_kernelILb1ELi32ELi6ELi3ELb0ELb1ELb1ELb0ELb1ELb0EEEviiPKi") \
+        == "_ZN12_GLOBAL__N_120bsr32_f32_cs2_kernelILb1ELb0ELb1ELb0ELb1ELb0EEEviiPKi"
+    assert kid.renamed("_Z1aILb1EEvPf") == "_Z1aILb1EEvPf"
+
+
+def test_renamed_kernels_compare_through_the_map():
+    """A body that refers to the kernel's own symbol follows the rename; without the map
+    the two files share no kernel."""
+    ref = "s_getpc_b64 s[0:1]\n\ts_add_u32 s0, s0, {0}@rel32@lo+4"
+    a, b = _kernel(_OLD, 0, ref.format(_OLD)), _kernel(_NEW, 0, ref.format(_NEW))
+    pairs = kid.rename_map(a, b)
+    assert pairs == [(_OLD, _NEW)]
+    assert kid.compare(kid.apply_renames(a, pairs), b) == []
+    assert {k for k, _, _ in kid.compare(a, b)} == {"only in A", "only in B"}
+    changed = _kernel(_NEW, 0, ref.format(_NEW), vgpr=9)
+    got = kid.compare(kid.apply_renames(a, pairs), changed)
+    assert [(k, n) for k, n, _ in got] == [("descriptor", _NEW)], got
+
+
+def test_a_kernel_gone_from_the_new_file_gets_no_pair():
+    assert kid.rename_map(_kernel(_OLD, 0), _kernel("_Z1aILb1EEvPf", 0)) == []

@@ -11,7 +11,16 @@ when every kernel is the same. This compares what matters, per kernel:
 
 It diffs whole streams and looks for no particular instruction.
 
-Usage: python tools/kernel_isa_diff.py A.s B.s     (exit status 1 if anything differs)
+A change that takes template parameters away renames kernels without touching them. A
+rename map, a text file of `old-symbol new-symbol` lines, is applied to the whole text of A
+first, so kernels are compared with their renamed selves and references inside bodies
+follow. The map is generated, not written: from the `.amdhsa_kernel` lists of the old and
+the new assembly and DROPPED below, which template-argument positions each kernel lost.
+
+Usage: python tools/kernel_isa_diff.py A.s B.s [rename_map.txt]
+           (exit status 1 if anything differs)
+       python tools/kernel_isa_diff.py --rename-map OLD.s NEW.s [OLD2.s NEW2.s ...]
+           (prints the map of every pair of files, release and TUNING say, as one)
 """
 from __future__ import annotations
 
@@ -21,6 +30,56 @@ import sys
 _KERNEL = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
 _ENTRY = re.compile(r"^([^\s:]+):")
 _LOCAL = re.compile(r"\.L([A-Za-z_]+)(\d+)_(\d+)")
+
+# kernel -> the 0-based positions of the template arguments it lost (each was the same
+# value at every launch site and is a constant of the kernel body now)
+DROPPED = {
+    "bsr32_f32_mfma_kernel": (3,),           # VAR
+    "bsr16_f32_mfma_kernel": (3,),           # VAR
+    "bsr16_f16_mfma_kernel": (3,),           # VAR
+    "bsr32_f32_lds_kernel": (1, 2, 4, 6),    # D, XM, HB, PAIR
+    "bsr32_f32_cs2_kernel": (1, 2, 3, 5),    # XM, P, NA, PK
+    "bsr32_f32_panel_kernel": (2,),          # D
+    "bsr16_cm_kernel": (2, 3, 4),            # D, DA, WPE
+    "bsr16_f16_cs_kernel": (1, 2, 3, 4, 6, 7),  # P, NA, DA, CAP, CST, COLS
+}
+# a kernel's own name and its template arguments inside a mangled symbol: literals
+# (Lb1E, Li32E) and builtin types (f, DF16_), none of which is a substitution candidate,
+# so the rest of the symbol is unchanged when some go
+_TEMPLATE_ID = re.compile("(%s)I((?:L[a-z]n?\\d+E|DF16_|[a-z])+)E" %
+                          "|".join(f"{len(k)}{k}" for k in DROPPED))
+_TEMPLATE_ARG = re.compile(r"L[a-z]n?\d+E|DF16_|[a-z]")
+
+
+def kernel_names(text: str) -> list[str]:
+    return re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
+
+
+def renamed(symbol: str) -> str:
+    """`symbol` without the template arguments DROPPED lists for its kernel."""
+    def drop(m: re.Match) -> str:
+        gone = DROPPED[m.group(1).lstrip("0123456789")]
+        args = _TEMPLATE_ARG.findall(m.group(2))
+        return "%sI%sE" % (m.group(1), "".join(a for i, a in enumerate(args) if i not in gone))
+    return _TEMPLATE_ID.sub(drop, symbol, count=1)
+
+
+def rename_map(old: str, new: str) -> list[tuple[str, str]]:
+    """(old symbol, new symbol) for every kernel of `old` that DROPPED renames. Each new
+    symbol must be a kernel of `new` and no two old ones may share it; a kernel that is
+    gone from `new` altogether (its old name and its new one) gets no pair."""
+    have = set(kernel_names(new))
+    pairs = [(k, renamed(k)) for k in kernel_names(old)]
+    pairs = [(k, r) for k, r in pairs if r != k and r in have]
+    assert len({r for _, r in pairs}) == len(pairs), "two kernels renamed to one symbol"
+    return sorted(pairs)
+
+
+def apply_renames(text: str, pairs) -> str:
+    """Every old symbol of `pairs` replaced by its new one, longest first."""
+    for old, new in sorted(pairs, key=lambda p: -len(p[0])):
+        text = text.replace(old, new)
+    return text
 
 
 def _strip(line: str) -> str:
@@ -87,14 +146,25 @@ def compare(a: str, b: str) -> list[tuple[str, str, str]]:
     return out
 
 
+def _read(path: str) -> str:
+    with open(path) as f:
+        return f.read()
+
+
 def main(argv: list[str]) -> int:
-    if len(argv) != 3:
+    if len(argv) >= 4 and argv[1] == "--rename-map" and len(argv) % 2 == 0:
+        pairs = set()
+        for old, new in zip(argv[2::2], argv[3::2]):
+            pairs |= set(rename_map(_read(old), _read(new)))
+        for old, new in sorted(pairs):
+            print(old, new)
+        return 0
+    if len(argv) not in (3, 4) or argv[1].startswith("--"):
         print(__doc__)
         return 2
-    with open(argv[1]) as f:
-        a = f.read()
-    with open(argv[2]) as f:
-        b = f.read()
+    a, b = _read(argv[1]), _read(argv[2])
+    if len(argv) == 4:
+        a = apply_renames(a, [ln.split() for ln in _read(argv[3]).splitlines() if ln.strip()])
     findings = compare(a, b)
     for kind, kernel, detail in findings:
         print(f"{kind}: {kernel}: {detail}" if detail else f"{kind}: {kernel}")
