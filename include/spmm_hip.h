@@ -120,7 +120,9 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *     spmm_set_csr_waves_per_cu), spmm_csrmm_hot_f32, spmm_bsrmm_ex_f32 / _f16
  *     / _f64 (SPMM_BSR_SMALL_GROUPED included), spmm_hybrid_csrmm_f32 /
  *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 and
- *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 (which keep
+ *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 and their multi-head forms
+ *     spmm_sddmm_csr_heads_f32, spmm_edge_softmax_csr_heads_f32 /
+ *     _bwd_csr_heads_f32 and spmm_csrmm_heads_f32 (which keep
  *     nothing in the handle's buffers), and the filling call of a group
  *     analysis. The setters of handle options are host-only: what they set is
  *     baked into the launches captured after them.
@@ -806,6 +808,89 @@ spmm_status_t spmm_edge_softmax_csr_f32(spmm_handle_t handle, int m, int nnz,
 spmm_status_t spmm_edge_softmax_bwd_csr_f32(spmm_handle_t handle, int m, int nnz,
                                             const int* csrRowPtr, spmm_index_base_t base,
                                             const float* y, const float* g, float* gx);
+
+/* The three ops of a graph attention layer over `heads` heads in one call each (no
+ * reference counterpart; csrc/heads_kernels.hip): the sampled product
+ * (the logits), the edge softmax with its backward, and the CSR product on per-head
+ * values. They replace the loop over heads of the single-head entries above and take the
+ * layouts graph frameworks use:
+ *   per-edge values (outVal, x, y, g, gx, csrVal): fp32 [nnz, heads], contiguous, element
+ *     (p, h) at p * heads + h, p the position as in the single-head entries (the same
+ *     base, the same csrRowPtr[0] > base views, the same clamping on the device);
+ *   per-node features (X, Y, B, C): row-major [rows, ld], ld >= heads * d counted in
+ *     floats, head h in the columns [h d, (h + 1) d): a contiguous [rows, heads, d].
+ * The contract is per head the written rule of the single-head entry, bit for bit:
+ *   spmm_sddmm_csr_heads_*: outVal[p, h] has the bits of spmm_sddmm_csr_f32 with n = d on
+ *     X + h d, Y + h d and the same ldx / ldy (G(d) chains and their butterfly). It does
+ *     not depend on alignment, ld, the grid or heads.
+ *   spmm_edge_softmax_csr_heads_* / _bwd_: column h of the result has the bits of
+ *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 on column h of the input (EXP, pieces of
+ *     1024, 64 chains, butterfly). Heads never mix: a row made non-finite in head h
+ *     leaves the other heads' bits alone. y may be exactly x, gx may be exactly g.
+ *   spmm_csrmm_heads_*: C[i, h d + c] = epi(sum over the row's positions p of
+ *     csrVal[p, h] * B[col(p), h d + c]) under the piece rule of the CSR product
+ *     (DESIGN.md §3c), at every d: the row's L nonzeros are cut into pieces of
+ *     max(128, ceil(L / 64)) nonzeros from its start, each piece a sequential chain
+ *     acc = fma(val, b, acc) from +0, the pieces added left to right from -0 (an empty
+ *     row is +0), then alpha * x, or fma(beta, C, alpha * x) when beta != 0. These are
+ *     the bits of spmm_csrmm_ex_f32 under SPMM_CSR_SEQUENTIAL_ROWS on (csrVal[:, h],
+ *     B[:, h d .. (h + 1) d)). Row-major B and C only. Sums start from +0, subnormals
+ *     are kept, and a non-finite csrVal[p, h] or B element reaches exactly the outputs
+ *     that reference it.
+ *   heads = 1 equals the single-head entries bit for bit (the product: under
+ *     SPMM_CSR_SEQUENTIAL_ROWS).
+ * Checks: those of the single-head entry of each op in its order (spmm_csrmm_ex_f32's for
+ *   the product, with ldb, ldc >= heads * d), and
+ *     heads < 1                    SPMM_STATUS_INVALID_VALUE, with the negative sizes;
+ *     nnz * heads > INT_MAX        SPMM_STATUS_NOT_SUPPORTED;
+ *     d > 1024 (sampled product)   SPMM_STATUS_NOT_SUPPORTED (loop over column blocks of
+ *                                  the single-head entry instead);
+ *     heads * d > 65535 * 64 (device product)
+ *                                  SPMM_STATUS_NOT_SUPPORTED (the column tiles of 64 are one
+ *                                  extent of the grid);
+ *   the two after the quick returns (m == 0 or nnz == 0; the product: m == 0 or d == 0)
+ *   and before anything is read or queued.
+ * The _host_ forms take host pointers and state the rules in executable form (worker
+ *   threads like the other host conversions); they also refuse a decreasing row pointer,
+ *   csrRowPtr[0] below the base, csrRowPtr[m] - base above nnz and, where there are column
+ *   indices, a column outside [0, k). The device forms equal them bit for bit
+ *   (tests/test_gpu_heads.py): a NULL handle is SPMM_STATUS_NOT_INITIALIZED before the
+ *   other checks; there is no device-side validation (positions are clamped to [0, nnz],
+ *   rows to [0, m)); each is one kernel on the handle's stream, takes nothing from the
+ *   handle's buffers, uses no atomics, does not synchronise or read back, and may be
+ *   captured into a graph. spmm_set_csr_waves_per_cu sizes the grids of all four; no grid
+ *   changes a bit. A row of more than 1024 positions (softmax) or
+ *   128 nonzeros (product) is done by the one workgroup that owns it. */
+spmm_status_t spmm_sddmm_csr_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
+                                            const int* csrRowPtr, const int* csrColInd,
+                                            spmm_index_base_t base, const float* X, int ldx,
+                                            const float* Y, int ldy, float beta, float* outVal);
+spmm_status_t spmm_sddmm_csr_heads_f32(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                       int heads, float alpha, const int* csrRowPtr,
+                                       const int* csrColInd, spmm_index_base_t base,
+                                       const float* X, int ldx, const float* Y, int ldy,
+                                       float beta, float* outVal);
+spmm_status_t spmm_edge_softmax_csr_heads_host_f32(int m, int nnz, int heads,
+                                                   const int* csrRowPtr, spmm_index_base_t base,
+                                                   const float* x, float* y);
+spmm_status_t spmm_edge_softmax_csr_heads_f32(spmm_handle_t handle, int m, int nnz, int heads,
+                                              const int* csrRowPtr, spmm_index_base_t base,
+                                              const float* x, float* y);
+spmm_status_t spmm_edge_softmax_bwd_csr_heads_host_f32(int m, int nnz, int heads,
+                                                       const int* csrRowPtr,
+                                                       spmm_index_base_t base, const float* y,
+                                                       const float* g, float* gx);
+spmm_status_t spmm_edge_softmax_bwd_csr_heads_f32(spmm_handle_t handle, int m, int nnz, int heads,
+                                                  const int* csrRowPtr, spmm_index_base_t base,
+                                                  const float* y, const float* g, float* gx);
+spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
+                                        const int* csrRowPtr, const int* csrColInd,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const float* B, int ldb, float beta, float* C, int ldc);
+spmm_status_t spmm_csrmm_heads_f32(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                   float alpha, const int* csrRowPtr, const int* csrColInd,
+                                   const float* csrVal, spmm_index_base_t base, const float* B,
+                                   int ldb, float beta, float* C, int ldc);
 
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's

@@ -226,6 +226,72 @@ spmm_status_t spmm_edge_softmax_bwd_csr_f32(spmm_handle_t handle, int m, int nnz
   return launch_edge_softmax(handle, true, m, nnz, csrRowPtr, (int)base, y, g, gx);
 }
 
+// The multi-head entries: the single-head entry's checks in its order, heads < 1 with the
+// negative sizes, and after the quick returns the shapes the kernels do not index.
+spmm_status_t spmm_sddmm_csr_heads_f32(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                       int heads, float alpha, const int* csrRowPtr,
+                                       const int* csrColInd, spmm_index_base_t base,
+                                       const float* X, int ldx, const float* Y, int ldy,
+                                       float beta, float* outVal) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < (long long)heads * d || ldy < (long long)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !csrColInd || !outVal || (d > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((long long)nnz * heads > INT32_MAX || d > 1024) return SPMM_STATUS_NOT_SUPPORTED;
+  return launch_sddmm_heads(handle, m, d, nnz, heads, csrRowPtr, csrColInd, (int)base, X, ldx, Y,
+                            ldy, alpha, beta, outVal);
+}
+
+spmm_status_t spmm_edge_softmax_csr_heads_f32(spmm_handle_t handle, int m, int nnz, int heads,
+                                              const int* csrRowPtr, spmm_index_base_t base,
+                                              const float* x, float* y) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !x || !y)) return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((long long)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  return launch_edge_softmax_heads(handle, false, m, nnz, heads, csrRowPtr, (int)base, x, nullptr,
+                                   y);
+}
+
+spmm_status_t spmm_edge_softmax_bwd_csr_heads_f32(spmm_handle_t handle, int m, int nnz, int heads,
+                                                  const int* csrRowPtr, spmm_index_base_t base,
+                                                  const float* y, const float* g, float* gx) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !y || !g || !gx)) return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((long long)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  return launch_edge_softmax_heads(handle, true, m, nnz, heads, csrRowPtr, (int)base, y, g, gx);
+}
+
+spmm_status_t spmm_csrmm_heads_f32(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                   float alpha, const int* csrRowPtr, const int* csrColInd,
+                                   const float* csrVal, spmm_index_base_t base, const float* B,
+                                   int ldb, float beta, float* C, int ldc) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || d == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && (!csrColInd || !csrVal)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < (long long)heads * d || ldc < (long long)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  // column tiles are the grid's y extent: at most 65535 tiles of 64 columns
+  if ((long long)nnz * heads > INT32_MAX || (long long)heads * d > 65535ll * 64)
+    return SPMM_STATUS_NOT_SUPPORTED;
+  return launch_csrmm_heads(handle, m, d, nnz, heads, csrRowPtr, csrColInd, csrVal, (int)base, B,
+                            ldb, alpha, beta, C, ldc);
+}
+
 spmm_status_t spmm_csr_hot_analysis(spmm_handle_t handle, int n, int k, int nnz,
                                     const int* csrColInd, spmm_index_base_t base,
                                     long long hotBytes, int* csrColIndHot) {

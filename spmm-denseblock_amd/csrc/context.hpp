@@ -193,6 +193,21 @@ spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* 
 spmm_status_t launch_edge_softmax(spmm_context* ctx, bool bwd, int m, int nnz, const int* rowptr,
                                   int base, const float* u, const float* v, float* o);
 
+// The three ops over `heads` heads in one launch each (heads_kernels.hip): per-edge values
+// [nnz, heads], per-node features with head h in the columns [h d, (h + 1) d). One launch,
+// no workspace; nnz * heads fits an int (and d <= 1024 for the sampled product).
+spmm_status_t launch_sddmm_heads(spmm_context* ctx, int m, int d, int nnz, int heads,
+                                 const int* rowptr, const int* colind, int base, const float* X,
+                                 int ldx, const float* Y, int ldy, float alpha, float beta,
+                                 float* out);
+spmm_status_t launch_edge_softmax_heads(spmm_context* ctx, bool bwd, int m, int nnz, int heads,
+                                        const int* rowptr, int base, const float* u,
+                                        const float* v, float* o);
+spmm_status_t launch_csrmm_heads(spmm_context* ctx, int m, int d, int nnz, int heads,
+                                 const int* rowptr, const int* colind, const float* val, int base,
+                                 const float* B, int ldb, float alpha, float beta, float* C,
+                                 int ldc);
+
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst);
 spmm_status_t launch_transpose(spmm_context* ctx, int rows, int cols, const float* src,

@@ -466,6 +466,159 @@ spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrR
   return SPMM_STATUS_SUCCESS;
 }
 
+// The three ops over `heads` heads (include/spmm_hip.h): per-edge values
+// [nnz, heads], per-node features with head h in the columns [h d, (h + 1) d); per head the
+// rule of the single-head form above, so heads = 1 is that form bit for bit.
+spmm_status_t spmm_sddmm_csr_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
+                                            const int* csrRowPtr, const int* csrColInd,
+                                            spmm_index_base_t base, const float* X, int ldx,
+                                            const float* Y, int ldy, float beta, float* outVal) {
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < (int64_t)heads * d || ldy < (int64_t)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !csrColInd || !outVal || (d > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((int64_t)nnz * heads > INT32_MAX || d > 1024) return SPMM_STATUS_NOT_SUPPORTED;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)csrRowPtr[0] - ba, p1 = (int64_t)csrRowPtr[m] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (csrRowPtr[r + 1] < csrRowPtr[r]) ok = false;
+  });
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p)
+      if (csrColInd[p] - ba < 0 || csrColInd[p] - ba >= k) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  const int G = sddmm_group_lanes(d);
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    if (lo >= hi) return;
+    int r = (int)(std::upper_bound(csrRowPtr, csrRowPtr + m, (int)(p0 + lo + ba)) - csrRowPtr) - 1;
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p) {
+      while (p >= (int64_t)csrRowPtr[r + 1] - ba) ++r;
+      const float* xr = X + (int64_t)r * ldx;
+      const float* yr = Y + (int64_t)(csrColInd[p] - ba) * ldy;
+      for (int h = 0; h < heads; ++h) {
+        const float dot = sddmm_dot(xr + (int64_t)h * d, yr + (int64_t)h * d, d, G);
+        float& o = outVal[p * heads + h];
+        o = beta == 0.f ? alpha * dot : __builtin_fmaf(beta, o, alpha * dot);
+      }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+spmm_status_t spmm_edge_softmax_csr_heads_host_f32(int m, int nnz, int heads,
+                                                   const int* csrRowPtr, spmm_index_base_t base,
+                                                   const float* x, float* y) {
+  if (heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  bool done;
+  const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !x || !y, &done);
+  if (done) return st;
+  if ((int64_t)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  const int ba = (int)base;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, L = (int64_t)csrRowPtr[r + 1] - ba - a;
+      for (int h = 0; h < heads; ++h) {
+        const float* xr = x + a * heads + h;
+        float mx = -__builtin_inff();
+        for (int64_t q = 0; q < L; ++q) mx = __builtin_fmaxf(mx, xr[q * heads]);
+        const float s = softmax_row_sum(L, [&](float acc, int64_t q) {
+          return acc + spmm_rule::softmax_exp(xr[q * heads] - mx);
+        });
+        for (int64_t q = 0; q < L; ++q)
+          y[(a + q) * heads + h] = spmm_rule::softmax_exp(xr[q * heads] - mx) / s;
+      }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+spmm_status_t spmm_edge_softmax_bwd_csr_heads_host_f32(int m, int nnz, int heads,
+                                                       const int* csrRowPtr,
+                                                       spmm_index_base_t base, const float* y,
+                                                       const float* g, float* gx) {
+  if (heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  bool done;
+  const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !y || !g || !gx, &done);
+  if (done) return st;
+  if ((int64_t)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  const int ba = (int)base;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, L = (int64_t)csrRowPtr[r + 1] - ba - a;
+      for (int h = 0; h < heads; ++h) {
+        const float* yr = y + a * heads + h;
+        const float* gr = g + a * heads + h;
+        const float dsum = softmax_row_sum(L, [&](float acc, int64_t q) {
+          return __builtin_fmaf(yr[q * heads], gr[q * heads], acc);
+        });
+        for (int64_t q = 0; q < L; ++q) {
+          const float diff = gr[q * heads] - dsum;
+          gx[(a + q) * heads + h] = yr[q * heads] * diff;
+        }
+      }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+// The product's piece rule on the host: a row of L nonzeros is cut into
+// pieces of max(128, ceil(L / 64)) nonzeros from its start, each a sequential chain
+// fma(val, b, acc) from +0, the pieces added left to right from -0 (an empty row is +0).
+spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
+                                        const int* csrRowPtr, const int* csrColInd,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const float* B, int ldb, float beta, float* C, int ldc) {
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || d == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && (!csrColInd || !csrVal)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < (int64_t)heads * d || ldc < (int64_t)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if ((int64_t)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)csrRowPtr[0] - ba, p1 = (int64_t)csrRowPtr[m] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (csrRowPtr[r + 1] < csrRowPtr[r]) ok = false;
+  });
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p)
+      if (csrColInd[p] - ba < 0 || csrColInd[p] - ba >= k) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, b = (int64_t)csrRowPtr[r + 1] - ba;
+      const int64_t T = std::max<int64_t>(128, (b - a + 63) / 64);
+      for (int h = 0; h < heads; ++h)
+        for (int c = h * d; c < (h + 1) * d; ++c) {
+          volatile float x = b > a ? -0.f : 0.f;  // no reassociation of the piece sums
+          for (int64_t s = a; s < b; s += T) {
+            float acc = 0.f;
+            for (int64_t p = s; p < std::min(s + T, b); ++p)
+              acc = __builtin_fmaf(csrVal[p * heads + h],
+                                   B[(int64_t)(csrColInd[p] - ba) * ldb + c], acc);
+            x = x + acc;
+          }
+          float& o = C[r * ldc + c];
+          const float xs = x;
+          o = beta == 0.f ? alpha * xs : __builtin_fmaf(beta, o, alpha * xs);
+        }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------

@@ -22,6 +22,12 @@ row's positions (ops.edge_softmax / ops.edge_softmax_bwd), and the product on th
 
     a = edge_softmax(A, sddmm(A, H, H))           # nnz attention weights
     H1 = spmm(A, H, val=a)                        # backpropagates to H on all three paths
+
+sddmm_heads, edge_softmax_heads and spmm_heads are the same chain over several heads, one
+launch per op (ops.*_heads): features [rows, heads, d], edge values [nnz, heads]:
+
+    a = edge_softmax_heads(A, sddmm_heads(A, H, H))   # [nnz, heads]
+    H1 = spmm_heads(A, H, val=a)                      # [m, heads, d]
 """
 from __future__ import annotations
 
@@ -226,4 +232,127 @@ def sddmm(A: CsrMatrix, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
     return _Sddmm.apply(X, Y, A)
 
 
-__all__ = ["CsrMatrix", "spmm", "edge_softmax", "sddmm"]
+# ---------------------------------------------------------------- several heads
+# The same three functions over [nnz, heads] edge values and [rows, heads, d] features,
+# one launch per op (ops.*_heads): per head the bits of the one-head ops.
+
+def _product_heads(A: CsrMatrix, val: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    heads, d = B.shape[1], B.shape[2]
+    return ops.csrmm_heads(A.rowptr, A.colind, val, B, m=A.m, d=d, heads=heads, k=A.k)
+
+
+def _f32_cuda(where: str, t, nm: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"{where}: {nm} must be a float32 tensor on a HIP device")
+
+
+class _SpmmHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, B: torch.Tensor, val: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        B, val = B.detach().contiguous(), val.detach().contiguous()
+        ctx.save_for_backward(B, val)
+        return _product_heads(A, val, B)
+
+    @staticmethod
+    def backward(ctx, grad_C: torch.Tensor):
+        A = ctx.A
+        B, val = ctx.saved_tensors
+        grad_C = grad_C.contiguous()
+        grad_B = grad_val = None
+        if ctx.needs_input_grad[0]:
+            vt = torch.index_select(val, 0, A.t_perm())  # a row gather of [nnz, heads]
+            grad_B = _product_heads(A.t(), vt, grad_C)
+        if ctx.needs_input_grad[1]:
+            grad_val = ops.sddmm_heads(A.rowptr, A.colind, grad_C, B, m=A.m, k=A.k)
+        return grad_B, grad_val, None
+
+
+def spmm_heads(A: CsrMatrix, H: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
+    """C[i, h, :] = sum_p val[p, h] * H[col(p), h, :] on A's pattern (ops.csrmm_heads; H:
+    [k, heads, d], val: [nnz, heads], C: [m, heads, d]), one launch for all heads. The
+    backward gives grad_val = ops.sddmm_heads(grad_C, H) and grad_H = ops.csrmm_heads on
+    A.t()'s pattern with the rows val[A.t_perm()], each only when it is needed: the
+    transpose is not built for grad_val alone. No float atomics: two runs give the same
+    bits."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("spmm_heads: A must be a CsrMatrix")
+    _f32_cuda("spmm_heads", H, "H")
+    _f32_cuda("spmm_heads", val, "val")
+    if H.dim() != 3 or H.shape[0] != A.k:
+        raise ValueError(f"spmm_heads: H must be ({A.k}, heads, d), got {tuple(H.shape)}")
+    if val.dim() != 2 or val.shape != (A.colind.numel(), H.shape[1]):
+        raise ValueError(f"spmm_heads: val must be ({A.colind.numel()}, {H.shape[1]}), got "
+                         f"{tuple(val.shape)}")
+    return _SpmmHeads.apply(H, val, A)
+
+
+class _EdgeSoftmaxHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        y = ops.edge_softmax_heads(A.rowptr, x.detach().contiguous(), m=A.m)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y: torch.Tensor):
+        (y,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return ops.edge_softmax_bwd_heads(ctx.A.rowptr, y, grad_y.contiguous(), m=ctx.A.m), None
+
+
+def edge_softmax_heads(A: CsrMatrix, e: torch.Tensor) -> torch.Tensor:
+    """The softmax of every column of e ([nnz, heads]) over the positions of every row of
+    A's pattern (ops.edge_softmax_heads); the backward is ops.edge_softmax_bwd_heads on the
+    saved output. Heads never mix."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("edge_softmax_heads: A must be a CsrMatrix")
+    _f32_cuda("edge_softmax_heads", e, "e")
+    if e.dim() != 2 or e.shape[0] != A.colind.numel():
+        raise ValueError(f"edge_softmax_heads: e must be ({A.colind.numel()}, heads), got "
+                         f"{tuple(e.shape)}")
+    return _EdgeSoftmaxHeads.apply(e, A)
+
+
+class _SddmmHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, Y: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
+        ctx.A = A
+        X, Y = X.detach().contiguous(), Y.detach().contiguous()
+        ctx.save_for_backward(X, Y)
+        return ops.sddmm_heads(A.rowptr, A.colind, X, Y, m=A.m, k=A.k)
+
+    @staticmethod
+    def backward(ctx, ge: torch.Tensor):
+        A = ctx.A
+        X, Y = ctx.saved_tensors
+        ge = ge.contiguous()
+        grad_X = grad_Y = None
+        if ctx.needs_input_grad[0]:
+            grad_X = _product_heads(A, ge, Y)
+        if ctx.needs_input_grad[1]:
+            grad_Y = _product_heads(A.t(), torch.index_select(ge, 0, A.t_perm()), X)
+        return grad_X, grad_Y, None
+
+
+def sddmm_heads(A: CsrMatrix, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """e[p, h] = <X[row(p), h, :], Y[col(p), h, :]> on A's pattern (ops.sddmm_heads; X:
+    [m, heads, d], Y: [k, heads, d]), with grad_X = ops.csrmm_heads(A, ge, Y) and grad_Y =
+    ops.csrmm_heads on A.t() with the rows ge[A.t_perm()] applied to X, each only when it
+    is needed. X may be Y; autograd then adds the two."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("sddmm_heads: A must be a CsrMatrix")
+    for t, rows, nm in ((X, A.m, "X"), (Y, A.k, "Y")):
+        _f32_cuda("sddmm_heads", t, nm)
+        if t.dim() != 3 or t.shape[0] != rows:
+            raise ValueError(f"sddmm_heads: {nm} must be ({rows}, heads, d), got "
+                             f"{tuple(t.shape)}")
+    if X.shape[1:] != Y.shape[1:]:
+        raise ValueError("sddmm_heads: X and Y differ in heads or d")
+    return _SddmmHeads.apply(X, Y, A)
+
+
+__all__ = ["CsrMatrix", "spmm", "edge_softmax", "sddmm", "spmm_heads", "edge_softmax_heads",
+           "sddmm_heads"]

@@ -14,6 +14,9 @@ through the C ABI. The functions mirror the reference's operator interfaces:
   sddmm(...)          cusparseSDDMM's shape on a CSR pattern: out[p] = <X[row(p)], Y[col(p)]>
   edge_softmax(...) / edge_softmax_bwd(...)
                       softmax over the positions of every CSR row (DGL's edge_softmax)
+  sddmm_heads(...) / edge_softmax_heads(...) / edge_softmax_bwd_heads(...) / csrmm_heads(...)
+                      the three ops of graph attention over several heads in one launch
+                      each: edge values [nnz, heads], features [rows, heads, d]
 """
 from __future__ import annotations
 
@@ -319,6 +322,135 @@ def edge_softmax_bwd(rowptr: torch.Tensor, y: torch.Tensor, g: torch.Tensor, *,
     check(lib().spmm_edge_softmax_bwd_csr_f32(h.raw, m, nnz, _ptr(rowptr), base, _ptr(y), _ptr(g),
                                               _ptr(out)), "spmm_edge_softmax_bwd_csr_f32")
     return out
+
+
+def _rows_needed(where: str, t: torch.Tensor, rows: int, ld: int, w: int, nm: str) -> None:
+    if ld < w or (rows > 0 and t.numel() < (rows - 1) * ld + w):
+        raise ValueError(f"{where}: {nm} holds {t.numel()} floats, {rows} rows of {w} with "
+                         f"leading dimension {ld} need {max(rows - 1, 0) * ld + w}")
+
+
+def sddmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *,
+                m: int | None = None, d: int | None = None, heads: int | None = None, k: int,
+                ldx: int | None = None, ldy: int | None = None, out: torch.Tensor | None = None,
+                alpha: float = 1.0, beta: float = 0.0, base: int = 0,
+                handle: Handle | None = None) -> torch.Tensor:
+    """sddmm over `heads` heads in one launch (spmm_sddmm_csr_heads_f32): out[p, h] =
+    alpha * <X[row(p), h d : (h + 1) d], Y[col(p), h d : (h + 1) d]> (+ beta * out[p, h]),
+    per head the bits of sddmm with n = d. X ([m, heads, d]) and Y ([k, heads, d]) are
+    row-major fp32 with leading dimensions ldx, ldy (default heads * d; heads and d default
+    to a 3-D X's). out is [nnz, heads] (default: a new tensor). One kernel: no
+    synchronisation, no workspace, capturable; the bits equal prep.sddmm_heads's."""
+    for t, dt, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                      (X, torch.float32, "X"), (Y, torch.float32, "Y")):
+        _need(t, dt, nm)
+    m = rowptr.numel() - 1 if m is None else m
+    if heads is None or d is None:
+        if X.dim() != 3:
+            raise ValueError("sddmm_heads: heads and d are needed when X is not a 3-D tensor")
+        heads, d = X.shape[1], X.shape[2]
+    w = max(heads, 0) * d
+    ldx = w if ldx is None else ldx
+    ldy = w if ldy is None else ldy
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"sddmm_heads: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    _rows_needed("sddmm_heads", X, m, ldx, w, "X")
+    _rows_needed("sddmm_heads", Y, k, ldy, w, "Y")
+    if out is None:
+        out = torch.empty((colind.numel(), max(heads, 0)), dtype=torch.float32,
+                          device=colind.device)
+    _need(out, torch.float32, "out")
+    if out.numel() < colind.numel() * max(heads, 0):
+        raise ValueError("sddmm_heads: out is shorter than [nnz, heads]")
+    h = handle or default_handle()
+    check(lib().spmm_sddmm_csr_heads_f32(h.raw, m, d, k, colind.numel(), heads, alpha,
+                                         _ptr(rowptr), _ptr(colind), base, _ptr(X), ldx, _ptr(Y),
+                                         ldy, beta, _ptr(out)), "spmm_sddmm_csr_heads_f32")
+    return out
+
+
+def _edge_softmax_heads_args(where: str, rowptr: torch.Tensor, m: int | None, arrays, out):
+    _need(rowptr, torch.int32, "rowptr")
+    m = rowptr.numel() - 1 if m is None else m
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"{where}: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    shape = arrays[0][1].shape
+    for nm, t in arrays:
+        _need(t, torch.float32, nm)
+        if t.dim() != 2 or t.shape != shape:
+            raise ValueError(f"{where}: {nm} must be [nnz, heads], got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rowptr.device)
+    _need(out, torch.float32, "out")
+    if out.shape != shape:
+        raise ValueError(f"{where}: out must be {tuple(shape)}, got {tuple(out.shape)}")
+    return m, shape[0], shape[1], out
+
+
+def edge_softmax_heads(rowptr: torch.Tensor, x: torch.Tensor, *, m: int | None = None,
+                       base: int = 0, out: torch.Tensor | None = None,
+                       handle: Handle | None = None) -> torch.Tensor:
+    """edge_softmax over every head in one launch (spmm_edge_softmax_csr_heads_f32): x is
+    [nnz, heads], column h of out has the bits of edge_softmax on column h of x; heads
+    never mix. out: default a new tensor, may be x itself. One kernel: no synchronisation,
+    no workspace, no atomics, capturable; the bits equal prep.edge_softmax_heads's."""
+    m, nnz, heads, out = _edge_softmax_heads_args("edge_softmax_heads", rowptr, m, (("x", x),),
+                                                  out)
+    h = handle or default_handle()
+    check(lib().spmm_edge_softmax_csr_heads_f32(h.raw, m, nnz, heads, _ptr(rowptr), base, _ptr(x),
+                                                _ptr(out)), "spmm_edge_softmax_csr_heads_f32")
+    return out
+
+
+def edge_softmax_bwd_heads(rowptr: torch.Tensor, y: torch.Tensor, g: torch.Tensor, *,
+                           m: int | None = None, base: int = 0, out: torch.Tensor | None = None,
+                           handle: Handle | None = None) -> torch.Tensor:
+    """The backward of edge_softmax_heads (spmm_edge_softmax_bwd_csr_heads_f32): y and g
+    are [nnz, heads], column h of out has the bits of edge_softmax_bwd on their columns h.
+    out may be g itself. The bits equal prep.edge_softmax_bwd_heads's."""
+    m, nnz, heads, out = _edge_softmax_heads_args("edge_softmax_bwd_heads", rowptr, m,
+                                                  (("y", y), ("g", g)), out)
+    h = handle or default_handle()
+    check(lib().spmm_edge_softmax_bwd_csr_heads_f32(h.raw, m, nnz, heads, _ptr(rowptr), base,
+                                                    _ptr(y), _ptr(g), _ptr(out)),
+          "spmm_edge_softmax_bwd_csr_heads_f32")
+    return out
+
+
+def csrmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B: torch.Tensor, *,
+                m: int | None = None, d: int, heads: int, k: int, ldb: int | None = None,
+                C: torch.Tensor | None = None, ldc: int | None = None, alpha: float = 1.0,
+                beta: float = 0.0, base: int = 0, handle: Handle | None = None) -> torch.Tensor:
+    """The CSR product over `heads` heads in one launch (spmm_csrmm_heads_f32):
+    C[i, h d + c] = alpha * sum_p val[p, h] * B[col(p), h d + c] (+ beta * C), per head the
+    bits of csrmm under SPMM_CSR_SEQUENTIAL_ROWS (the piece rule at every d). val is
+    [nnz, heads]; B ([k, heads, d]) and C ([m, heads, d]; default a new tensor) are
+    row-major fp32 with leading dimensions ldb, ldc (default heads * d). One kernel: no
+    synchronisation, no workspace, no atomics, capturable; the bits equal
+    prep.csrmm_heads's."""
+    for t, dt, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                      (val, torch.float32, "val"), (B, torch.float32, "B")):
+        _need(t, dt, nm)
+    m = rowptr.numel() - 1 if m is None else m
+    w = max(heads, 0) * d
+    ldb = w if ldb is None else ldb
+    ldc = w if ldc is None else ldc
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"csrmm_heads: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    if val.numel() < colind.numel() * max(heads, 0):
+        raise ValueError("csrmm_heads: val is shorter than [nnz, heads]")
+    _rows_needed("csrmm_heads", B, k, ldb, w, "B")
+    if C is None:
+        if ldc != w:
+            raise ValueError("csrmm_heads: a padded ldc needs a C of the caller's")
+        C = torch.empty((m, max(heads, 0), d), dtype=torch.float32, device=B.device)
+    _need(C, torch.float32, "C")
+    _rows_needed("csrmm_heads", C, m, ldc, w, "C")
+    h = handle or default_handle()
+    check(lib().spmm_csrmm_heads_f32(h.raw, m, d, k, colind.numel(), heads, alpha, _ptr(rowptr),
+                                     _ptr(colind), _ptr(val), base, _ptr(B), ldb, beta, _ptr(C),
+                                     ldc), "spmm_csrmm_heads_f32")
+    return C
 
 
 def csr_hot_analysis(colind: torch.Tensor, *, n: int, k: int, base: int = 0,

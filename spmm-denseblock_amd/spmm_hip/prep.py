@@ -3,6 +3,7 @@
 Thin wrappers over the C ABI of libspmm_hip.so:
   csr2bsr / bsr2csr / csr2csc / sddmm / calculate_nnzb / partition_rows   (include/spmm_hip.h)
   edge_softmax / edge_softmax_bwd                                        (include/spmm_hip.h)
+  sddmm_heads / edge_softmax_heads / edge_softmax_bwd_heads / csrmm_heads (include/spmm_hip.h)
   rng_seed / random_array / random_csr / random_bsr /
   load_csr / dump_csr / load_graph / save_csr_bin / load_csr_bin / load_csr_cached /
   powerlaw_csr / community_csr                                  (include/spmm_host.h)
@@ -185,6 +186,101 @@ def edge_softmax_bwd(rowptr, y, g, *, m: int | None = None, base: int = 0,
                                                    _p(out)),
           "spmm_edge_softmax_bwd_csr_host_f32")
     return out
+
+
+def _f32c(where: str, nm: str, a, size: int | None = None) -> None:
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous:
+        raise TypeError(f"{where}: {nm} must be a C-contiguous float32 array")
+    if size is not None and a.size < size:
+        raise ValueError(f"{where}: {nm} holds {a.size} floats, needs {size}")
+
+
+def sddmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, X, Y, *,
+                ldx: int | None = None, ldy: int | None = None, out=None, alpha: float = 1.0,
+                beta: float = 0.0, base: int = 0) -> np.ndarray:
+    """spmm_sddmm_csr_heads_host_f32: out[p, h] = alpha * <X[row(p), h d : (h + 1) d],
+    Y[col(p), h d : (h + 1) d]> (+ beta * out[p, h]): prep.sddmm with n = d per head, bit
+    for bit. X ([m, heads, d]) and Y ([k, heads, d]): float32 with leading dimensions ldx,
+    ldy (default heads * d). out: float32 [nnz, heads] (default zeros; returned)."""
+    rowptr, colind = _i32(rowptr), _i32(colind)
+    if rowptr.size != m + 1:
+        raise ValueError(f"sddmm_heads: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    w = max(heads, 0) * d
+    ldx = w if ldx is None else ldx
+    ldy = w if ldy is None else ldy
+    for a, rows, ld, nm in ((X, m, ldx, "X"), (Y, k, ldy, "Y")):
+        _f32c("sddmm_heads", nm, a, (rows - 1) * ld + w if rows > 0 and ld >= w else None)
+    if out is None:
+        out = np.zeros((colind.size, max(heads, 0)), dtype=np.float32)
+    _f32c("sddmm_heads", "out", out, colind.size * max(heads, 0))
+    check(lib().spmm_sddmm_csr_heads_host_f32(m, d, k, colind.size, heads, alpha, _p(rowptr),
+                                              _p(colind), base, _p(X), ldx, _p(Y), ldy, beta,
+                                              _p(out)), "spmm_sddmm_csr_heads_host_f32")
+    return out
+
+
+def _softmax_heads_args(where: str, rowptr, m, arrays, out):
+    rowptr = _i32(rowptr)
+    m = rowptr.size - 1 if m is None else m
+    if m < 0 or rowptr.size != m + 1:
+        raise ValueError(f"{where}: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    shape = arrays[0][1].shape
+    for nm, a in arrays + ((("out", out),) if out is not None else ()):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or \
+                not a.flags.c_contiguous or a.shape != shape:
+            raise TypeError(f"{where}: {nm} must be a contiguous float32 array [nnz, heads]")
+    if out is None:
+        out = np.zeros(shape, dtype=np.float32)
+    return rowptr, m, shape[0], shape[1], out
+
+
+def edge_softmax_heads(rowptr, x, *, m: int | None = None, base: int = 0, out=None) -> np.ndarray:
+    """spmm_edge_softmax_csr_heads_host_f32: x is [nnz, heads]; column h of out is
+    prep.edge_softmax of column h of x, bit for bit. out may be x itself."""
+    rowptr, m, nnz, heads, out = _softmax_heads_args("edge_softmax_heads", rowptr, m,
+                                                     (("x", x),), out)
+    check(lib().spmm_edge_softmax_csr_heads_host_f32(m, nnz, heads, _p(rowptr), base, _p(x),
+                                                     _p(out)),
+          "spmm_edge_softmax_csr_heads_host_f32")
+    return out
+
+
+def edge_softmax_bwd_heads(rowptr, y, g, *, m: int | None = None, base: int = 0,
+                           out=None) -> np.ndarray:
+    """spmm_edge_softmax_bwd_csr_heads_host_f32: y and g are [nnz, heads]; column h of out
+    is prep.edge_softmax_bwd of their columns h, bit for bit. out may be g itself."""
+    rowptr, m, nnz, heads, out = _softmax_heads_args("edge_softmax_bwd_heads", rowptr, m,
+                                                     (("y", y), ("g", g)), out)
+    check(lib().spmm_edge_softmax_bwd_csr_heads_host_f32(m, nnz, heads, _p(rowptr), base, _p(y),
+                                                         _p(g), _p(out)),
+          "spmm_edge_softmax_bwd_csr_heads_host_f32")
+    return out
+
+
+def csrmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, val, B, *,
+                ldb: int | None = None, C=None, ldc: int | None = None, alpha: float = 1.0,
+                beta: float = 0.0, base: int = 0) -> np.ndarray:
+    """spmm_csrmm_heads_host_f32: C[i, h d + c] = alpha * sum_p val[p, h] * B[col(p), h d + c]
+    (+ beta * C) under the piece rule of the CSR product, per head. val: float32
+    [nnz, heads]; B ([k, heads, d]) and C ([m, heads, d]; default zeros; returned): float32
+    with leading dimensions ldb, ldc (default heads * d)."""
+    rowptr, colind = _i32(rowptr), _i32(colind)
+    if rowptr.size != m + 1:
+        raise ValueError(f"csrmm_heads: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    w = max(heads, 0) * d
+    ldb = w if ldb is None else ldb
+    ldc = w if ldc is None else ldc
+    _f32c("csrmm_heads", "val", val, colind.size * max(heads, 0))
+    _f32c("csrmm_heads", "B", B, (k - 1) * ldb + w if k > 0 and ldb >= w else None)
+    if C is None:
+        C = np.zeros(max(m - 1, 0) * ldc + w if m > 0 else 0, dtype=np.float32)
+        if ldc == w:
+            C = C.reshape(m, max(heads, 0), d)
+    _f32c("csrmm_heads", "C", C, (m - 1) * ldc + w if m > 0 and ldc >= w else None)
+    check(lib().spmm_csrmm_heads_host_f32(m, d, k, colind.size, heads, alpha, _p(rowptr),
+                                          _p(colind), _p(val), base, _p(B), ldb, beta, _p(C),
+                                          ldc), "spmm_csrmm_heads_host_f32")
+    return C
 
 
 def calculate_nnzb(n: int, rowptr, colind, bs: int) -> int:
