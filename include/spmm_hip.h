@@ -121,8 +121,8 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *     / _f64 (SPMM_BSR_SMALL_GROUPED included), spmm_hybrid_csrmm_f32 /
  *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 and
  *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 and their multi-head forms
- *     spmm_sddmm_csr_heads_f32, spmm_edge_softmax_csr_heads_f32 /
- *     _bwd_csr_heads_f32 and spmm_csrmm_heads_f32 (which keep
+ *     spmm_sddmm_csr_heads_f32 / _f16 / _bf16, spmm_edge_softmax_csr_heads_f32 /
+ *     _bwd_csr_heads_f32 and spmm_csrmm_heads_f32 / _f16 / _bf16 (which keep
  *     nothing in the handle's buffers), and the filling call of a group
  *     analysis. The setters of handle options are host-only: what they set is
  *     baked into the launches captured after them.
@@ -891,6 +891,66 @@ spmm_status_t spmm_csrmm_heads_f32(spmm_handle_t handle, int m, int d, int k, in
                                    float alpha, const int* csrRowPtr, const int* csrColInd,
                                    const float* csrVal, spmm_index_base_t base, const float* B,
                                    int ldb, float beta, float* C, int ldc);
+
+/* The multi-head sampled product and product on fp16 and bf16 per-node features (no
+ * reference counterpart; csrc/heads_half_kernels.hip). The arguments are
+ * those of spmm_sddmm_csr_heads_f32 / spmm_csrmm_heads_f32, with X, Y / B given as 16-bit
+ * patterns (IEEE binary16 for _f16, bfloat16 for _bf16, as in spmm_csrmm_ex_f16) and ldx,
+ * ldy / ldb >= heads * d counted in elements. Edge values (outVal, csrVal), alpha, beta, C
+ * and ldc stay fp32: the weights come from the fp32 edge softmax, which has no half form.
+ * Contract: outVal / C equal, bit for bit and signed zeros included, what the _f32 entry
+ *   gives on the operands widened to fp32 (both widenings are exact, subnormals included;
+ *   nothing is flushed): the G(d) chains and butterfly for the sampled product, the piece
+ *   rule at every d for the product. The bits do not depend on the grid, ld, alignment,
+ *   heads, the vector width or the load path: a base that is only 2- or 4-byte aligned, or
+ *   an odd ld, takes narrower loads and gives the same bits. A non-finite feature reaches
+ *   exactly the outputs that reference it.
+ * Everything else is the _f32 entries': the checks, their order, the quick returns and the
+ *   refusals (heads < 1; nnz * heads > INT_MAX; d > 1024 for the sampled product;
+ *   heads * d > 65535 * 64 for the device product); heads = 1 serves one head; the device
+ *   entries queue one kernel on the handle's stream, take nothing from the handle's
+ *   buffers, use no atomics, do not synchronise and may be captured;
+ *   spmm_set_csr_waves_per_cu sizes the grids. The _host_ forms widen the operands and run
+ *   the fp32 host forms, so they state the rule in executable form and refuse what those
+ *   refuse.
+ * Speed: DESIGN.md §4k's table (profiles/heads_half/summary.json); the gathered bytes per
+ *   nonzero and head go from 4 d to 2 d. */
+spmm_status_t spmm_sddmm_csr_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
+                                            const int* csrRowPtr, const int* csrColInd,
+                                            spmm_index_base_t base, const uint16_t* X, int ldx,
+                                            const uint16_t* Y, int ldy, float beta, float* outVal);
+spmm_status_t spmm_sddmm_csr_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
+                                             const int* csrRowPtr, const int* csrColInd,
+                                             spmm_index_base_t base, const uint16_t* X, int ldx,
+                                             const uint16_t* Y, int ldy, float beta,
+                                             float* outVal);
+spmm_status_t spmm_sddmm_csr_heads_f16(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                       int heads, float alpha, const int* csrRowPtr,
+                                       const int* csrColInd, spmm_index_base_t base,
+                                       const uint16_t* X, int ldx, const uint16_t* Y, int ldy,
+                                       float beta, float* outVal);
+spmm_status_t spmm_sddmm_csr_heads_bf16(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                        int heads, float alpha, const int* csrRowPtr,
+                                        const int* csrColInd, spmm_index_base_t base,
+                                        const uint16_t* X, int ldx, const uint16_t* Y, int ldy,
+                                        float beta, float* outVal);
+spmm_status_t spmm_csrmm_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
+                                        const int* csrRowPtr, const int* csrColInd,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const uint16_t* B, int ldb, float beta, float* C, int ldc);
+spmm_status_t spmm_csrmm_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
+                                         const int* csrRowPtr, const int* csrColInd,
+                                         const float* csrVal, spmm_index_base_t base,
+                                         const uint16_t* B, int ldb, float beta, float* C,
+                                         int ldc);
+spmm_status_t spmm_csrmm_heads_f16(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                   float alpha, const int* csrRowPtr, const int* csrColInd,
+                                   const float* csrVal, spmm_index_base_t base, const uint16_t* B,
+                                   int ldb, float beta, float* C, int ldc);
+spmm_status_t spmm_csrmm_heads_bf16(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                    float alpha, const int* csrRowPtr, const int* csrColInd,
+                                    const float* csrVal, spmm_index_base_t base, const uint16_t* B,
+                                    int ldb, float beta, float* C, int ldc);
 
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's

@@ -103,6 +103,46 @@ spmm_status_t bsrmm_staged(spmm_context* ctx, int kb, int n, int bs, const T* B,
   return launch(Bt, n);
 }
 
+// spmm_sddmm_csr_heads_f16 / _bf16: spmm_sddmm_csr_heads_f32's checks in its order
+spmm_status_t sddmm_heads_half(spmm_context* handle, bool bf16, int m, int d, int k, int nnz,
+                               int heads, float alpha, const int* csrRowPtr, const int* csrColInd,
+                               spmm_index_base_t base, const uint16_t* X, int ldx,
+                               const uint16_t* Y, int ldy, float beta, float* outVal) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < (long long)heads * d || ldy < (long long)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!csrRowPtr || !csrColInd || !outVal || (d > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((long long)nnz * heads > INT32_MAX || d > 1024) return SPMM_STATUS_NOT_SUPPORTED;
+  if (d == 0)  // no feature is read: the fp32 entry's fill
+    return launch_sddmm_heads(handle, m, 0, nnz, heads, csrRowPtr, csrColInd, (int)base, nullptr,
+                              ldx, nullptr, ldy, alpha, beta, outVal);
+  return launch_sddmm_heads_half(handle, bf16, m, d, nnz, heads, csrRowPtr, csrColInd, (int)base,
+                                 X, ldx, Y, ldy, alpha, beta, outVal);
+}
+
+// spmm_csrmm_heads_f16 / _bf16: spmm_csrmm_heads_f32's checks in its order
+spmm_status_t csrmm_heads_half(spmm_context* handle, bool bf16, int m, int d, int k, int nnz,
+                               int heads, float alpha, const int* csrRowPtr, const int* csrColInd,
+                               const float* csrVal, spmm_index_base_t base, const uint16_t* B,
+                               int ldb, float beta, float* C, int ldc) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || d == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && (!csrColInd || !csrVal)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < (long long)heads * d || ldc < (long long)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if ((long long)nnz * heads > INT32_MAX || (long long)heads * d > 65535ll * 64)
+    return SPMM_STATUS_NOT_SUPPORTED;
+  return launch_csrmm_heads_half(handle, bf16, m, d, nnz, heads, csrRowPtr, csrColInd, csrVal,
+                                 (int)base, B, ldb, alpha, beta, C, ldc);
+}
+
 // [a, a + bytes) and [b, b + bytes) share a byte
 bool overlaps(const void* a, const void* b, size_t bytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
@@ -290,6 +330,43 @@ spmm_status_t spmm_csrmm_heads_f32(spmm_handle_t handle, int m, int d, int k, in
     return SPMM_STATUS_NOT_SUPPORTED;
   return launch_csrmm_heads(handle, m, d, nnz, heads, csrRowPtr, csrColInd, csrVal, (int)base, B,
                             ldb, alpha, beta, C, ldc);
+}
+
+// The fp16 / bf16-feature forms of the sampled product and the product (bit patterns; edge
+// values, alpha, beta, outVal and C stay fp32): the fp32 entries' checks, quick returns and
+// refusals, and their bits on the widened operands.
+spmm_status_t spmm_sddmm_csr_heads_f16(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                       int heads, float alpha, const int* csrRowPtr,
+                                       const int* csrColInd, spmm_index_base_t base,
+                                       const uint16_t* X, int ldx, const uint16_t* Y, int ldy,
+                                       float beta, float* outVal) {
+  return sddmm_heads_half(handle, false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
+                          ldx, Y, ldy, beta, outVal);
+}
+
+spmm_status_t spmm_sddmm_csr_heads_bf16(spmm_handle_t handle, int m, int d, int k, int nnz,
+                                        int heads, float alpha, const int* csrRowPtr,
+                                        const int* csrColInd, spmm_index_base_t base,
+                                        const uint16_t* X, int ldx, const uint16_t* Y, int ldy,
+                                        float beta, float* outVal) {
+  return sddmm_heads_half(handle, true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
+                          ldx, Y, ldy, beta, outVal);
+}
+
+spmm_status_t spmm_csrmm_heads_f16(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                   float alpha, const int* csrRowPtr, const int* csrColInd,
+                                   const float* csrVal, spmm_index_base_t base, const uint16_t* B,
+                                   int ldb, float beta, float* C, int ldc) {
+  return csrmm_heads_half(handle, false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
+                          base, B, ldb, beta, C, ldc);
+}
+
+spmm_status_t spmm_csrmm_heads_bf16(spmm_handle_t handle, int m, int d, int k, int nnz, int heads,
+                                    float alpha, const int* csrRowPtr, const int* csrColInd,
+                                    const float* csrVal, spmm_index_base_t base, const uint16_t* B,
+                                    int ldb, float beta, float* C, int ldc) {
+  return csrmm_heads_half(handle, true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
+                          base, B, ldb, beta, C, ldc);
 }
 
 spmm_status_t spmm_csr_hot_analysis(spmm_handle_t handle, int n, int k, int nnz,

@@ -208,6 +208,19 @@ spmm_status_t launch_csrmm_heads(spmm_context* ctx, int m, int d, int nnz, int h
                                  const float* B, int ldb, float alpha, float beta, float* C,
                                  int ldc);
 
+// The sampled product and the product on fp16 (bf16 false) or bf16 (true) features given as
+// bit patterns (heads_half_kernels.hip): the same kernel text as the two above
+// (heads_impl.hpp), ldx / ldy / ldb in elements; d > 0 (d == 0 reads no features and goes
+// to launch_sddmm_heads).
+spmm_status_t launch_sddmm_heads_half(spmm_context* ctx, bool bf16, int m, int d, int nnz,
+                                      int heads, const int* rowptr, const int* colind, int base,
+                                      const uint16_t* X, int ldx, const uint16_t* Y, int ldy,
+                                      float alpha, float beta, float* out);
+spmm_status_t launch_csrmm_heads_half(spmm_context* ctx, bool bf16, int m, int d, int nnz,
+                                      int heads, const int* rowptr, const int* colind,
+                                      const float* val, int base, const uint16_t* B, int ldb,
+                                      float alpha, float beta, float* C, int ldc);
+
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst);
 spmm_status_t launch_transpose(spmm_context* ctx, int rows, int cols, const float* src,

@@ -622,6 +622,130 @@ spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads,
 }  // extern "C"
 
 // ----------------------------------------------------------------------------
+// The fp16 / bf16-feature forms of the multi-head sampled product and product (DESIGN.md
+// §4k): the rule is the fp32 form's on the widened operands, and that is how it is stated.
+// ----------------------------------------------------------------------------
+namespace {
+
+// binary16 -> binary32, exact (subnormals included); a NaN comes out quiet, as from the
+// hardware's conversion.
+inline float widen_f16(uint16_t h) {
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, f = h & 0x3ffu;
+  uint32_t u;
+  if (e == 0) {
+    float v = (float)f * 0x1p-24f;  // f 2^-24: exact
+    std::memcpy(&u, &v, 4);
+    u |= sign;
+  } else if (e == 31) {
+    u = sign | 0x7f800000u | (f ? 0x400000u | (f << 13) : 0u);
+  } else {
+    u = sign | ((e + 112u) << 23) | (f << 13);
+  }
+  float x;
+  std::memcpy(&x, &u, 4);
+  return x;
+}
+
+// bfloat16 -> binary32: the pattern is the upper half.
+inline float widen_bf16(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float x;
+  std::memcpy(&x, &u, 4);
+  return x;
+}
+
+// The first w columns of `rows` rows with leading dimension ld (>= w), widened, at the
+// same ld; what lies between the rows is left zero and never read.
+std::vector<float> widened(const uint16_t* a, int64_t rows, int64_t ld, int64_t w, bool bf16) {
+  std::vector<float> out(rows > 0 && w > 0 ? (size_t)((rows - 1) * ld + w) : 0, 0.f);
+  spmm_host::parallel_for(rows, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      for (int64_t c = 0; c < w; ++c)
+        out[r * ld + c] = bf16 ? widen_bf16(a[r * ld + c]) : widen_f16(a[r * ld + c]);
+  });
+  return out;
+}
+
+// The fp32 host form's checks up to the point where it reads X and Y (its order), then the
+// fp32 host form itself on the widened X and Y: the rest of its checks are its own.
+spmm_status_t sddmm_heads_host_half(bool bf16, int m, int d, int k, int nnz, int heads,
+                                    float alpha, const int* rp, const int* ci,
+                                    spmm_index_base_t base, const uint16_t* X, int ldx,
+                                    const uint16_t* Y, int ldy, float beta, float* outVal) {
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldx < (int64_t)heads * d || ldy < (int64_t)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if (nnz > 0 && (!rp || !ci || !outVal || (d > 0 && (!X || !Y))))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || nnz == 0) return SPMM_STATUS_SUCCESS;
+  if ((int64_t)nnz * heads > INT32_MAX || d > 1024) return SPMM_STATUS_NOT_SUPPORTED;
+  const std::vector<float> Xf = widened(X, m, ldx, (int64_t)heads * d, bf16);
+  const std::vector<float> Yf = widened(Y, k, ldy, (int64_t)heads * d, bf16);
+  // (d == 0: both copies are empty, and the fp32 form reads neither)
+  return spmm_sddmm_csr_heads_host_f32(m, d, k, nnz, heads, alpha, rp, ci, base, Xf.data(), ldx,
+                                       Yf.data(), ldy, beta, outVal);
+}
+
+spmm_status_t csrmm_heads_host_half(bool bf16, int m, int d, int k, int nnz, int heads,
+                                    float alpha, const int* rp, const int* ci, const float* val,
+                                    spmm_index_base_t base, const uint16_t* B, int ldb, float beta,
+                                    float* C, int ldc) {
+  if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || d == 0) return SPMM_STATUS_SUCCESS;
+  if (!rp || !C || (k > 0 && !B) || (nnz > 0 && (!ci || !val))) return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < (int64_t)heads * d || ldc < (int64_t)heads * d) return SPMM_STATUS_INVALID_VALUE;
+  if ((int64_t)nnz * heads > INT32_MAX) return SPMM_STATUS_NOT_SUPPORTED;
+  const std::vector<float> Bf = widened(B, k, ldb, (int64_t)heads * d, bf16);
+  // k == 0: B may be null and Bf is empty; the fp32 form then refuses any column index
+  return spmm_csrmm_heads_host_f32(m, d, k, nnz, heads, alpha, rp, ci, val, base,
+                                   k > 0 ? Bf.data() : nullptr, ldb, beta, C, ldc);
+}
+
+}  // namespace
+
+extern "C" {
+
+spmm_status_t spmm_sddmm_csr_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
+                                            const int* csrRowPtr, const int* csrColInd,
+                                            spmm_index_base_t base, const uint16_t* X, int ldx,
+                                            const uint16_t* Y, int ldy, float beta, float* outVal) {
+  return sddmm_heads_host_half(false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
+                               ldx, Y, ldy, beta, outVal);
+}
+
+spmm_status_t spmm_sddmm_csr_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
+                                             const int* csrRowPtr, const int* csrColInd,
+                                             spmm_index_base_t base, const uint16_t* X, int ldx,
+                                             const uint16_t* Y, int ldy, float beta,
+                                             float* outVal) {
+  return sddmm_heads_host_half(true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
+                               ldx, Y, ldy, beta, outVal);
+}
+
+spmm_status_t spmm_csrmm_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
+                                        const int* csrRowPtr, const int* csrColInd,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const uint16_t* B, int ldb, float beta, float* C,
+                                        int ldc) {
+  return csrmm_heads_host_half(false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
+                               base, B, ldb, beta, C, ldc);
+}
+
+spmm_status_t spmm_csrmm_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
+                                         const int* csrRowPtr, const int* csrColInd,
+                                         const float* csrVal, spmm_index_base_t base,
+                                         const uint16_t* B, int ldb, float beta, float* C,
+                                         int ldc) {
+  return csrmm_heads_host_half(true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
+                               base, B, ldb, beta, C, ldc);
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------
 // divide_matrix (divide.cu:52-127) with values.
 // ----------------------------------------------------------------------------
 namespace {

@@ -210,6 +210,22 @@ _PROTOS = {
                                           c_int, _P, c_int, c_float, _P, c_int]),
     "spmm_csrmm_heads_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
                                      c_int, _P, c_int, c_float, _P, c_int]),
+    "spmm_sddmm_csr_heads_host_f16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                                              c_int, _P, c_int, _P, c_int, c_float, _P]),
+    "spmm_sddmm_csr_heads_f16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                                         c_int, _P, c_int, _P, c_int, c_float, _P]),
+    "spmm_csrmm_heads_host_f16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
+                                          c_int, _P, c_int, c_float, _P, c_int]),
+    "spmm_csrmm_heads_f16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
+                                     c_int, _P, c_int, c_float, _P, c_int]),
+    "spmm_sddmm_csr_heads_host_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                                              c_int, _P, c_int, _P, c_int, c_float, _P]),
+    "spmm_sddmm_csr_heads_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                                         c_int, _P, c_int, _P, c_int, c_float, _P]),
+    "spmm_csrmm_heads_host_bf16": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
+                                          c_int, _P, c_int, c_float, _P, c_int]),
+    "spmm_csrmm_heads_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
+                                     c_int, _P, c_int, c_float, _P, c_int]),
     "spmm_xcoo2csr": (c_int, [_P, _P, c_int, c_int, _P, c_int]),
     # spmm_multi.h
     "spmm_multi_create": (c_int, [POINTER(c_void_p), c_int, _P]),

@@ -28,6 +28,10 @@ launch per op (ops.*_heads): features [rows, heads, d], edge values [nnz, heads]
 
     a = edge_softmax_heads(A, sddmm_heads(A, H, H))   # [nnz, heads]
     H1 = spmm_heads(A, H, val=a)                      # [m, heads, d]
+
+H may be float16 or bfloat16 there (ops.*_heads on half features): the logits, the softmax
+and every edge gradient stay float32, the kernels accumulate in float32, and a result that
+takes the features' place (H1, H.grad) is cast to H's type once, round to nearest even.
 """
 from __future__ import annotations
 
@@ -246,13 +250,19 @@ def _f32_cuda(where: str, t, nm: str) -> None:
         raise TypeError(f"{where}: {nm} must be a float32 tensor on a HIP device")
 
 
+def _feature_cuda(where: str, t, nm: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype not in ops._FEATURE_TYPES or not t.is_cuda:
+        raise TypeError(f"{where}: {nm} must be a float32, float16 or bfloat16 tensor on a HIP "
+                        f"device")
+
+
 class _SpmmHeads(torch.autograd.Function):
     @staticmethod
     def forward(ctx, B: torch.Tensor, val: torch.Tensor, A: CsrMatrix) -> torch.Tensor:
         ctx.A = A
         B, val = B.detach().contiguous(), val.detach().contiguous()
         ctx.save_for_backward(B, val)
-        return _product_heads(A, val, B)
+        return _product_heads(A, val, B).to(B.dtype)  # (fp32 features: the same tensor)
 
     @staticmethod
     def backward(ctx, grad_C: torch.Tensor):
@@ -262,7 +272,7 @@ class _SpmmHeads(torch.autograd.Function):
         grad_B = grad_val = None
         if ctx.needs_input_grad[0]:
             vt = torch.index_select(val, 0, A.t_perm())  # a row gather of [nnz, heads]
-            grad_B = _product_heads(A.t(), vt, grad_C)
+            grad_B = _product_heads(A.t(), vt, grad_C).to(B.dtype)
         if ctx.needs_input_grad[1]:
             grad_val = ops.sddmm_heads(A.rowptr, A.colind, grad_C, B, m=A.m, k=A.k)
         return grad_B, grad_val, None
@@ -274,10 +284,14 @@ def spmm_heads(A: CsrMatrix, H: torch.Tensor, val: torch.Tensor) -> torch.Tensor
     backward gives grad_val = ops.sddmm_heads(grad_C, H) and grad_H = ops.csrmm_heads on
     A.t()'s pattern with the rows val[A.t_perm()], each only when it is needed: the
     transpose is not built for grad_val alone. No float atomics: two runs give the same
-    bits."""
+    bits.
+    H may be float16 or bfloat16 with float32 val: C is then the fp32 product's bits cast to
+    H's type (one round to nearest even), so grad_C arrives in H's type and both backward
+    ops run on half features: grad_H is their fp32 result cast to H's type, grad_val stays
+    float32."""
     if not isinstance(A, CsrMatrix):
         raise TypeError("spmm_heads: A must be a CsrMatrix")
-    _f32_cuda("spmm_heads", H, "H")
+    _feature_cuda("spmm_heads", H, "H")
     _f32_cuda("spmm_heads", val, "val")
     if H.dim() != 3 or H.shape[0] != A.k:
         raise ValueError(f"spmm_heads: H must be ({A.k}, heads, d), got {tuple(H.shape)}")
@@ -331,9 +345,9 @@ class _SddmmHeads(torch.autograd.Function):
         ge = ge.contiguous()
         grad_X = grad_Y = None
         if ctx.needs_input_grad[0]:
-            grad_X = _product_heads(A, ge, Y)
+            grad_X = _product_heads(A, ge, Y).to(X.dtype)
         if ctx.needs_input_grad[1]:
-            grad_Y = _product_heads(A.t(), torch.index_select(ge, 0, A.t_perm()), X)
+            grad_Y = _product_heads(A.t(), torch.index_select(ge, 0, A.t_perm()), X).to(Y.dtype)
         return grad_X, grad_Y, None
 
 
@@ -341,16 +355,20 @@ def sddmm_heads(A: CsrMatrix, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
     """e[p, h] = <X[row(p), h, :], Y[col(p), h, :]> on A's pattern (ops.sddmm_heads; X:
     [m, heads, d], Y: [k, heads, d]), with grad_X = ops.csrmm_heads(A, ge, Y) and grad_Y =
     ops.csrmm_heads on A.t() with the rows ge[A.t_perm()] applied to X, each only when it
-    is needed. X may be Y; autograd then adds the two."""
+    is needed. X may be Y; autograd then adds the two.
+    X and Y may both be float16 or both bfloat16: e stays float32, and each gradient is the
+    fp32 product's bits cast to the features' type."""
     if not isinstance(A, CsrMatrix):
         raise TypeError("sddmm_heads: A must be a CsrMatrix")
     for t, rows, nm in ((X, A.m, "X"), (Y, A.k, "Y")):
-        _f32_cuda("sddmm_heads", t, nm)
+        _feature_cuda("sddmm_heads", t, nm)
         if t.dim() != 3 or t.shape[0] != rows:
             raise ValueError(f"sddmm_heads: {nm} must be ({rows}, heads, d), got "
                              f"{tuple(t.shape)}")
     if X.shape[1:] != Y.shape[1:]:
         raise ValueError("sddmm_heads: X and Y differ in heads or d")
+    if X.dtype != Y.dtype:
+        raise TypeError(f"sddmm_heads: X and Y must share a dtype, got {X.dtype} and {Y.dtype}")
     return _SddmmHeads.apply(X, Y, A)
 
 

@@ -330,6 +330,28 @@ def _rows_needed(where: str, t: torch.Tensor, rows: int, ld: int, w: int, nm: st
                          f"leading dimension {ld} need {max(rows - 1, 0) * ld + w}")
 
 
+_FEATURE_TYPES = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
+
+
+def _feature_suffix(where: str, feats) -> str:
+    """The entry suffix for the per-node feature tensors `feats` ((name, tensor) pairs): all
+    float32 ("f32", today's entries), all float16 ("f16") or all bfloat16 ("bf16"). Half
+    features exist on the device only."""
+    t0 = feats[0][1]
+    for nm, t in feats:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{nm} must be a torch.Tensor")
+        if t.dtype not in _FEATURE_TYPES:
+            raise TypeError(f"{where}: {nm} must be float32, float16 or bfloat16, got {t.dtype}")
+        if t.dtype != t0.dtype:
+            raise TypeError(f"{where}: {feats[0][0]} and {nm} must share a dtype, got "
+                            f"{t0.dtype} and {t.dtype}")
+        if t.dtype != torch.float32 and not t.is_cuda:
+            raise TypeError(f"{where}: {nm} is a {t.dtype} tensor on the CPU; half features "
+                            f"are served on a HIP device only")
+    return _FEATURE_TYPES[t0.dtype]
+
+
 def sddmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *,
                 m: int | None = None, d: int | None = None, heads: int | None = None, k: int,
                 ldx: int | None = None, ldy: int | None = None, out: torch.Tensor | None = None,
@@ -340,9 +362,12 @@ def sddmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: 
     per head the bits of sddmm with n = d. X ([m, heads, d]) and Y ([k, heads, d]) are
     row-major fp32 with leading dimensions ldx, ldy (default heads * d; heads and d default
     to a 3-D X's). out is [nnz, heads] (default: a new tensor). One kernel: no
-    synchronisation, no workspace, capturable; the bits equal prep.sddmm_heads's."""
+    synchronisation, no workspace, capturable; the bits equal prep.sddmm_heads's.
+    X and Y may both be float16 or both bfloat16 (spmm_sddmm_csr_heads_f16 / _bf16; ldx, ldy
+    in elements): out stays fp32 and has the bits of the call on X.float(), Y.float()."""
+    ty = _feature_suffix("sddmm_heads", (("X", X), ("Y", Y)))
     for t, dt, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
-                      (X, torch.float32, "X"), (Y, torch.float32, "Y")):
+                      (X, X.dtype, "X"), (Y, Y.dtype, "Y")):
         _need(t, dt, nm)
     m = rowptr.numel() - 1 if m is None else m
     if heads is None or d is None:
@@ -363,9 +388,10 @@ def sddmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, X: torch.Tensor, Y: 
     if out.numel() < colind.numel() * max(heads, 0):
         raise ValueError("sddmm_heads: out is shorter than [nnz, heads]")
     h = handle or default_handle()
-    check(lib().spmm_sddmm_csr_heads_f32(h.raw, m, d, k, colind.numel(), heads, alpha,
-                                         _ptr(rowptr), _ptr(colind), base, _ptr(X), ldx, _ptr(Y),
-                                         ldy, beta, _ptr(out)), "spmm_sddmm_csr_heads_f32")
+    entry = "spmm_sddmm_csr_heads_" + ty
+    check(getattr(lib(), entry)(h.raw, m, d, k, colind.numel(), heads, alpha, _ptr(rowptr),
+                                _ptr(colind), base, _ptr(X), ldx, _ptr(Y), ldy, beta, _ptr(out)),
+          entry)
     return out
 
 
@@ -427,9 +453,12 @@ def csrmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B
     [nnz, heads]; B ([k, heads, d]) and C ([m, heads, d]; default a new tensor) are
     row-major fp32 with leading dimensions ldb, ldc (default heads * d). One kernel: no
     synchronisation, no workspace, no atomics, capturable; the bits equal
-    prep.csrmm_heads's."""
+    prep.csrmm_heads's.
+    B may be float16 or bfloat16 (spmm_csrmm_heads_f16 / _bf16; ldb in elements): val and C
+    stay fp32 and C has the bits of the call on B.float()."""
+    ty = _feature_suffix("csrmm_heads", (("B", B),))
     for t, dt, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
-                      (val, torch.float32, "val"), (B, torch.float32, "B")):
+                      (val, torch.float32, "val"), (B, B.dtype, "B")):
         _need(t, dt, nm)
     m = rowptr.numel() - 1 if m is None else m
     w = max(heads, 0) * d
@@ -447,9 +476,10 @@ def csrmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B
     _need(C, torch.float32, "C")
     _rows_needed("csrmm_heads", C, m, ldc, w, "C")
     h = handle or default_handle()
-    check(lib().spmm_csrmm_heads_f32(h.raw, m, d, k, colind.numel(), heads, alpha, _ptr(rowptr),
-                                     _ptr(colind), _ptr(val), base, _ptr(B), ldb, beta, _ptr(C),
-                                     ldc), "spmm_csrmm_heads_f32")
+    entry = "spmm_csrmm_heads_" + ty
+    check(getattr(lib(), entry)(h.raw, m, d, k, colind.numel(), heads, alpha, _ptr(rowptr),
+                                _ptr(colind), _ptr(val), base, _ptr(B), ldb, beta, _ptr(C), ldc),
+          entry)
     return C
 
 

@@ -195,27 +195,51 @@ def _f32c(where: str, nm: str, a, size: int | None = None) -> None:
         raise ValueError(f"{where}: {nm} holds {a.size} floats, needs {size}")
 
 
+def _feature_suffix(where: str, arrays, bf16: bool) -> str:
+    """The entry suffix for the per-node feature arrays `arrays` ((name, array) pairs of one
+    dtype): float32 -> "f32", float16 -> "f16", uint16 with bf16=True -> "bf16" (bfloat16
+    bit patterns: numpy has no such type)."""
+    dt = getattr(arrays[0][1], "dtype", None)
+    want = np.dtype(np.uint16) if bf16 else None
+    for nm, a in arrays:
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous or a.dtype != dt or \
+                (want is not None and a.dtype != want) or \
+                (want is None and a.dtype not in (np.float32, np.float16)):
+            raise TypeError(f"{where}: {nm} must be a C-contiguous float32 or float16 array, or "
+                            f"uint16 bfloat16 patterns with bf16=True (all of one type)")
+    return "bf16" if bf16 else "f16" if dt == np.float16 else "f32"
+
+
+def _holds(where: str, nm: str, a, size: int | None) -> None:
+    if size is not None and a.size < size:
+        raise ValueError(f"{where}: {nm} holds {a.size} elements, needs {size}")
+
+
 def sddmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, X, Y, *,
                 ldx: int | None = None, ldy: int | None = None, out=None, alpha: float = 1.0,
-                beta: float = 0.0, base: int = 0) -> np.ndarray:
+                beta: float = 0.0, base: int = 0, bf16: bool = False) -> np.ndarray:
     """spmm_sddmm_csr_heads_host_f32: out[p, h] = alpha * <X[row(p), h d : (h + 1) d],
     Y[col(p), h d : (h + 1) d]> (+ beta * out[p, h]): prep.sddmm with n = d per head, bit
     for bit. X ([m, heads, d]) and Y ([k, heads, d]): float32 with leading dimensions ldx,
-    ldy (default heads * d). out: float32 [nnz, heads] (default zeros; returned)."""
+    ldy (default heads * d). out: float32 [nnz, heads] (default zeros; returned).
+    X and Y may both be float16, or uint16 bfloat16 patterns with bf16=True
+    (spmm_sddmm_csr_heads_host_f16 / _bf16): the bits of the float32 form on the widened
+    arrays; out stays float32."""
     rowptr, colind = _i32(rowptr), _i32(colind)
     if rowptr.size != m + 1:
         raise ValueError(f"sddmm_heads: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
     w = max(heads, 0) * d
     ldx = w if ldx is None else ldx
     ldy = w if ldy is None else ldy
+    ty = _feature_suffix("sddmm_heads", (("X", X), ("Y", Y)), bf16)
     for a, rows, ld, nm in ((X, m, ldx, "X"), (Y, k, ldy, "Y")):
-        _f32c("sddmm_heads", nm, a, (rows - 1) * ld + w if rows > 0 and ld >= w else None)
+        _holds("sddmm_heads", nm, a, (rows - 1) * ld + w if rows > 0 and ld >= w else None)
     if out is None:
         out = np.zeros((colind.size, max(heads, 0)), dtype=np.float32)
     _f32c("sddmm_heads", "out", out, colind.size * max(heads, 0))
-    check(lib().spmm_sddmm_csr_heads_host_f32(m, d, k, colind.size, heads, alpha, _p(rowptr),
-                                              _p(colind), base, _p(X), ldx, _p(Y), ldy, beta,
-                                              _p(out)), "spmm_sddmm_csr_heads_host_f32")
+    entry = "spmm_sddmm_csr_heads_host_" + ty
+    check(getattr(lib(), entry)(m, d, k, colind.size, heads, alpha, _p(rowptr), _p(colind), base,
+                                _p(X), ldx, _p(Y), ldy, beta, _p(out)), entry)
     return out
 
 
@@ -259,11 +283,13 @@ def edge_softmax_bwd_heads(rowptr, y, g, *, m: int | None = None, base: int = 0,
 
 def csrmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, val, B, *,
                 ldb: int | None = None, C=None, ldc: int | None = None, alpha: float = 1.0,
-                beta: float = 0.0, base: int = 0) -> np.ndarray:
+                beta: float = 0.0, base: int = 0, bf16: bool = False) -> np.ndarray:
     """spmm_csrmm_heads_host_f32: C[i, h d + c] = alpha * sum_p val[p, h] * B[col(p), h d + c]
     (+ beta * C) under the piece rule of the CSR product, per head. val: float32
     [nnz, heads]; B ([k, heads, d]) and C ([m, heads, d]; default zeros; returned): float32
-    with leading dimensions ldb, ldc (default heads * d)."""
+    with leading dimensions ldb, ldc (default heads * d). B may be float16, or uint16
+    bfloat16 patterns with bf16=True (spmm_csrmm_heads_host_f16 / _bf16): the bits of the
+    float32 form on the widened B; val and C stay float32."""
     rowptr, colind = _i32(rowptr), _i32(colind)
     if rowptr.size != m + 1:
         raise ValueError(f"csrmm_heads: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
@@ -271,15 +297,16 @@ def csrmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, val, B, *,
     ldb = w if ldb is None else ldb
     ldc = w if ldc is None else ldc
     _f32c("csrmm_heads", "val", val, colind.size * max(heads, 0))
-    _f32c("csrmm_heads", "B", B, (k - 1) * ldb + w if k > 0 and ldb >= w else None)
+    ty = _feature_suffix("csrmm_heads", (("B", B),), bf16)
+    _holds("csrmm_heads", "B", B, (k - 1) * ldb + w if k > 0 and ldb >= w else None)
     if C is None:
         C = np.zeros(max(m - 1, 0) * ldc + w if m > 0 else 0, dtype=np.float32)
         if ldc == w:
             C = C.reshape(m, max(heads, 0), d)
     _f32c("csrmm_heads", "C", C, (m - 1) * ldc + w if m > 0 and ldc >= w else None)
-    check(lib().spmm_csrmm_heads_host_f32(m, d, k, colind.size, heads, alpha, _p(rowptr),
-                                          _p(colind), _p(val), base, _p(B), ldb, beta, _p(C),
-                                          ldc), "spmm_csrmm_heads_host_f32")
+    entry = "spmm_csrmm_heads_host_" + ty
+    check(getattr(lib(), entry)(m, d, k, colind.size, heads, alpha, _p(rowptr), _p(colind),
+                                _p(val), base, _p(B), ldb, beta, _p(C), ldc), entry)
     return C
 
 

@@ -42,6 +42,12 @@ DROPPED = {
     "bsr32_f32_panel_kernel": (2,),          # D
     "bsr16_cm_kernel": (2, 3, 4),            # D, DA, WPE
     "bsr16_f16_cs_kernel": (1, 2, 3, 4, 6, 7),  # P, NA, DA, CAP, CST, COLS
+    # These two gained a parameter (the storage type T, `float` in heads_kernels.hip): give
+    # the new assembly as OLD / A and the old one as NEW / B, so that the map takes T away.
+    # Their pointer parameters depend on T, so the parameter list is spelled differently too
+    # (PKT_ for PKf) and the other name is found by its template-id (rename_map).
+    "sddmm_heads_kernel": (0,),              # T
+    "csrmm_heads_kernel": (0,),              # T
 }
 # a kernel's own name and its template arguments inside a mangled symbol: literals
 # (Lb1E, Li32E) and builtin types (f, DF16_), none of which is a substitution candidate,
@@ -69,8 +75,22 @@ def rename_map(old: str, new: str) -> list[tuple[str, str]]:
     symbol must be a kernel of `new` and no two old ones may share it; a kernel that is
     gone from `new` altogether (its old name and its new one) gets no pair."""
     have = set(kernel_names(new))
-    pairs = [(k, renamed(k)) for k in kernel_names(old)]
-    pairs = [(k, r) for k, r in pairs if r != k and r in have]
+
+    def template_id(symbol: str) -> str | None:  # the symbol up to the end of its arguments
+        m = _TEMPLATE_ID.search(symbol)
+        return symbol[:m.end()] if m else None
+
+    def found(r: str) -> str | None:
+        """r itself, or the one kernel of `new` with r's template-id when a parameter
+        that went was a type the parameter list depends on."""
+        if r in have:
+            return r
+        tid = template_id(r)
+        same = [n for n in have if tid is not None and template_id(n) == tid]
+        return same[0] if len(same) == 1 else None
+
+    pairs = [(k, found(renamed(k))) for k in kernel_names(old) if renamed(k) != k]
+    pairs = [(k, r) for k, r in pairs if r is not None]
     assert len({r for _, r in pairs}) == len(pairs), "two kernels renamed to one symbol"
     return sorted(pairs)
 
