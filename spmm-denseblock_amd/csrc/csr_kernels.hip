@@ -492,12 +492,17 @@ static __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
   if (G > 0) {
     int colv[kR];
     float valv[kR];
+    // Positions past A1 - 1 are formed as unsigned and clamped as unsigned: the last chunk
+    // reaches up to kChunk * kU - 1 positions past A1, which passes INT_MAX when A1 (at most
+    // rowptr[m] - base) is within a chunk of it; as an int the sum would wrap below zero and
+    // the clamp would keep it (gs is aligned to kU only, so a chunk need not end on a multiple
+    // of kChunk * kU). gs, A0 and A1 are positions, never negative.
     auto load_chunk = [&](int c) {
-      const int cb = gs + c * (kChunk * kU) + kR * lane;
+      const unsigned cb = (unsigned)gs + (unsigned)c * (kChunk * kU) + (unsigned)(kR * lane);
       T raw[kR];  // the values as stored: widened once per lane below (fp16 input)
 #pragma unroll
       for (int r = 0; r < kR; ++r) {
-        const int idx = min(cb + r, A1 - 1);
+        const unsigned idx = min(cb + r, (unsigned)(A1 - 1));
         if constexpr (NT) {
           colv[r] = __builtin_nontemporal_load(colind + idx);
           raw[r] = __builtin_nontemporal_load(val + idx);
@@ -557,12 +562,14 @@ static __global__ __launch_bounds__(kWG) void csr_mergepath_kernel(
       }
     };
     auto consume = [&](float (&src)[kU][VEC], const float (&vsrc)[kU], int g) {
-      const int ag = gs + g * kU;
+      // a group is kU-aligned and begins below A1, so ag + u stays within INT_MAX (2^31 is a
+      // multiple of kU); unsigned only to read like load_chunk
+      const unsigned ag = (unsigned)gs + (unsigned)g * kU;
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
-        const int a = ag + u;
-        if (a >= A0 && a < A1) {
-          const int j = a - aoff;
+        const unsigned a = ag + u;
+        if (a >= (unsigned)A0 && a < (unsigned)A1) {
+          const int j = (int)(a - (unsigned)aoff);
           while (ps.ev <= j) event();  // ev is INT_MAX past the last event
 #pragma unroll
           for (int c = 0; c < VEC; ++c) acc[c] = __builtin_fmaf(vsrc[u], src[u][c], acc[c]);
@@ -775,7 +782,11 @@ __global__ __launch_bounds__(kWG) void csr_group_kernel(
   const int gs = A0 & ~(G - 1);
   const int S = j1 > j0 ? (A1 - gs + G - 1) / G : 0;
   auto load_idx = [&](int s, int& c, float& v) {
-    const int p = min(max(gs + G * s + grp, A0), A1 - 1);  // clamped: always a valid index
+    // clamped: always a valid index. A step is G-aligned and begins below A1, so the sum
+    // stays within INT_MAX (2^31 is a multiple of G); unsigned only to read like the main
+    // kernel's chunk loads, the one sum of this kind that could wrap.
+    const unsigned p = min(max((unsigned)gs + (unsigned)(G * s + grp), (unsigned)A0),
+                           (unsigned)(A1 - 1));
     if constexpr (NT) {
       c = __builtin_nontemporal_load(colind + p);
       v = __builtin_nontemporal_load(val + p);
@@ -793,9 +804,9 @@ __global__ __launch_bounds__(kWG) void csr_group_kernel(
   // One step's products: groups before an event (piece or row end) inside the
   // step belong to the piece that ends there.
   auto consume = [&](int s, const f32x4& b, float v) {
-    const int q0 = gs + G * s;
-    const int p = q0 + grp;
-    const bool ok = p >= A0 && p < A1;
+    const int q0 = gs + G * s;  // below A1
+    const unsigned p = (unsigned)q0 + (unsigned)grp;
+    const bool ok = p >= (unsigned)A0 && p < (unsigned)A1;
     f32x4 prod;
 #pragma unroll
     for (int c = 0; c < 4; ++c) prod[c] = ok ? v * b[c] : 0.f;

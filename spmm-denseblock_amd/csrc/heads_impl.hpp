@@ -225,8 +225,12 @@ __device__ __forceinline__ int find_row(const int* __restrict__ rowptr, int m, i
 }
 
 // G = G(d) lanes per virtual position q = p * heads + h; a lane holds up to NC chunks of
-// four columns (NC > 1 only at G = 64: d up to 1024). nnz * heads fits an int, so a
-// virtual position plus a few steps fits an unsigned. ldx, ldy count elements of T.
+// four columns (NC > 1 only at G = 64: d up to 1024). nnz * heads fits an int (the entries
+// refuse anything more), so a virtual position plus a few steps fits an unsigned: q0, q1 and
+// the share's start are long long, a share ends at b <= INT_MAX, and the last batch reaches
+// less than 2^10 virtual positions past it, as an unsigned clamped to b - 1 (held at
+// nnz * heads = INT_MAX - (INT_MAX mod heads) by tests/test_gpu_far_positions.py).
+// ldx, ldy count elements of T.
 template <typename T, int G, bool VEC>
 __global__ __launch_bounds__(kWG) void sddmm_heads_kernel(
     int m, int d, int nnz, int heads, const int* __restrict__ rowptr,

@@ -99,8 +99,11 @@ __device__ __forceinline__ void settle(T& x) {
 }
 
 // The positions of the pattern, clamped to what csrColInd / outVal hold (nnz is an int,
-// so a position fits 32 bits, and a position plus a few steps fits an unsigned), and
-// wave w's share [a, b): whole steps of S positions.
+// so a position fits 32 bits, and a position plus a few steps fits an unsigned: a share ends
+// at b <= INT_MAX and the last batch reaches at most PD * S + 63 < 2^10 positions past it;
+// every such sum in the kernels is an unsigned and is clamped to b - 1 as one; held at
+// rowptr[m] - base = INT_MAX by tests/test_gpu_far_positions.py), and wave w's share
+// [a, b): whole steps of S positions.
 struct Share {
   unsigned a, b;
 };

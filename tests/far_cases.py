@@ -255,6 +255,7 @@ _INT = {2: np.int16, 4: np.int32, 8: np.int64}
 # guard word does not): helpers' own for fp16 / fp32 / fp64, and one for bfloat16
 _SENTINEL = {2: 0x7C2A, 4: 0x7F80BEEF, 8: 0x7FF00000DEADBEEF}
 _SENTINEL_BF16 = 0x7FA5
+INT_TYPE, SENTINEL, SENTINEL_BF16 = _INT, _SENTINEL, _SENTINEL_BF16  # for tests/far_pos_cases.py
 
 
 class FarOperand:
@@ -283,13 +284,14 @@ class FarOperand:
 
 
 class Arena:
-    """One uninitialised device allocation of ARENA_BYTES. place() writes the used rows of
-    an operand (and their guards) with one strided copy (one per row where `rows` names the
-    rows of a sparser choice); nothing initialises the rest."""
+    """One uninitialised device allocation of BYTES (ARENA_BYTES; a subclass may set its own).
+    place() writes the used rows of an operand (and their guards) with one strided copy (one
+    per row where `rows` names the rows of a sparser choice); nothing initialises the rest."""
+    BYTES = ARENA_BYTES
 
     def __init__(self):
         import torch
-        self.buf = torch.empty(ARENA_BYTES, dtype=torch.uint8, device="cuda")
+        self.buf = torch.empty(self.BYTES, dtype=torch.uint8, device="cuda")
         assert self.buf.data_ptr() % 256 == 0
 
     def close(self):
@@ -310,7 +312,7 @@ class Arena:
         first = FAR_BASE // elem + off
         last_row = nrows - 1 if rows is None else int(max(rows))
         assert ld >= n + 2 * GUARD and first >= GUARD
-        assert (first + last_row * ld + n + GUARD) * elem <= ARENA_BYTES, "outside the arena"
+        assert (first + last_row * ld + n + GUARD) * elem <= self.BYTES, "outside the arena"
         host = np.empty((nrows, n + 2 * GUARD), it)
         bits = _SENTINEL_BF16 if dtype is torch.bfloat16 else _SENTINEL[elem]
         host[:] = np.array([bits], "u%d" % elem).view(it)[0]
