@@ -122,7 +122,8 @@ spmm_status_t spmm_get_stream(spmm_handle_t handle, void** stream);
  *     _ex_f32, spmm_bsrmm_grouped_f16 / _f32, spmm_sddmm_csr_f32 and
  *     spmm_edge_softmax_csr_f32 / _bwd_csr_f32 and their multi-head forms
  *     spmm_sddmm_csr_heads_f32 / _f16 / _bf16, spmm_edge_softmax_csr_heads_f32 /
- *     _bwd_csr_heads_f32 and spmm_csrmm_heads_f32 / _f16 / _bf16 (which keep
+ *     _bwd_csr_heads_f32 and spmm_csrmm_heads_f32 / _f16 / _bf16 and the max /
+ *     min reducers spmm_csrmm_reduce_f32 / _bwd_f32 (which keep
  *     nothing in the handle's buffers), and the filling call of a group
  *     analysis. The setters of handle options are host-only: what they set is
  *     baked into the launches captured after them.
@@ -951,6 +952,82 @@ spmm_status_t spmm_csrmm_heads_bf16(spmm_handle_t handle, int m, int d, int k, i
                                     float alpha, const int* csrRowPtr, const int* csrColInd,
                                     const float* csrVal, spmm_index_base_t base, const uint16_t* B,
                                     int ldb, float beta, float* C, int ldc);
+
+/* The max / min reducers of the CSR product with the winning positions, and their backward
+ * (no reference counterpart; csrc/reduce_kernels.hip): DGL's copy_u_max /
+ * u_mul_e_max, PyG's aggr = "max", torch.sparse.mm(A, B, reduce = "amax" | "amin"). A is
+ * m x k CSR, B [k, ldb], C [m, ldc], arg int [m, ldarg], all row-major; fp32.
+ * Forward, row i with the array positions [a, b), column j < n:
+ *   the term t_p = csrVal[p] * B[col(p), j]: one fp32 multiply, round to nearest, fused with
+ *     nothing, subnormals kept; with csrVal == NULL (the unweighted aggregation) t_p is
+ *     B[col(p), j] as stored;
+ *   the winner w for SPMM_REDUCE_MAX: the lowest p whose t_p is a NaN if there is one,
+ *     otherwise the lowest p with t_p >= t_q for every q under the IEEE comparison (+0 and
+ *     -0 tie, and the lower position wins); SPMM_REDUCE_MIN: the same with <=;
+ *   C[i, j] = t_w, the winner's own bits (the sign of a zero is the winner's; of a NaN only
+ *     NaN-ness is specified); arg[i, j] = w, a 0-based position into csrColInd / csrVal
+ *     whatever the index base; an empty row gives C = +0 and arg = -1.
+ *   C and arg are overwritten (no alpha, no beta). arg may be NULL (inference): it is then
+ *     neither computed nor written, and ldarg is not looked at.
+ *   Ordered by (is-NaN, value, -position) the combine is a commutative monoid: any
+ *     partition of a row over lanes, waves and workgroups gives the same C and arg, so the
+ *     bits depend on the row alone, not on the grid, ld, alignment or vector width.
+ * Backward: dB [k, lddb] from dC [m, lddc] and arg, over the CSR arrays of A^T (tRowPtr,
+ *   tColInd: k rows) and perm (perm[q] = the position in A of transposed position q:
+ *   spmm_csr2csc's perm); csrVal is in A's order, or NULL. Row c of A^T with the positions
+ *   [ta, tb), L = tb - ta, column j: walk q in order, i = tColInd[q] - base,
+ *   sel = (arg[i, j] == perm[q]), v = csrVal[perm[q]] (1.0f when NULL), and
+ *   acc = sel ? fma(v, dC[i, j], acc) : acc, associated by the product's piece rule
+ *   counted over all L positions, selected or not: pieces of max(128, ceil(L / 64))
+ *   positions from the row's start, each a chain from +0, the pieces added left to right
+ *   from -0; dB[c, j] is that sum (overwritten), +0 for an empty row, at every n. An
+ *   unselected position contributes nothing, even where v or dC is infinite or a NaN.
+ *   arg is only compared, never used as an index: a corrupt arg cannot make the entry read
+ *   out of bounds. With every position selected the result is spmm_csrmm_heads_host_f32
+ *   (heads = 1, alpha = 1, beta = 0) on the transposed arrays with the values
+ *   csrVal[perm], bit for bit. No float atomics anywhere.
+ * Checks, in spmm_csrmm_ex_f32's order: a NULL handle is SPMM_STATUS_NOT_INITIALIZED; a
+ *   negative size, an op or base that is not one of the enumerators: INVALID_VALUE; m == 0
+ *   or n == 0 (backward: k == 0 or n == 0) returns SUCCESS; then a NULL csrRowPtr or C, a
+ *   NULL B with k > 0, a NULL csrColInd with nnz > 0 (backward: a NULL tRowPtr or dB; with
+ *   nnz > 0 a NULL tColInd, perm, dC or arg), and ldb, ldc, ldarg (with arg), lddc or lddb
+ *   below n: INVALID_VALUE. nnz == 0 is no quick return: C is filled with +0 and arg with
+ *   -1, dB with +0. More than 65535 column tiles (n above 65535 * 64 at the narrowest
+ *   lane): SPMM_STATUS_NOT_SUPPORTED.
+ * The _host_ forms take host pointers and no handle and state the rules in executable form
+ *   (worker threads like the other host forms); they also refuse a decreasing row pointer,
+ *   a first entry below the base, a last entry - base above nnz, a column outside [0, k)
+ *   (backward: outside [0, m)) and a perm entry outside [0, nnz). The device forms equal
+ *   them bit for bit (tests/test_gpu_reduce.py); they do not validate (positions are
+ *   clamped to [0, nnz], rows to the row count, perm to [0, nnz) where it indexes csrVal).
+ * Graphs: each device entry is one kernel on the handle's stream, takes nothing from the
+ *   handle's buffers (no workspace, no tickets, no keys to initialise), does not
+ *   synchronise or read back, and may be captured. Every element offset of B, C, arg, dC
+ *   and dB is computed in 64 bits. spmm_set_csr_waves_per_cu sizes the grids; no grid
+ *   changes a bit. A row of more than 128 positions is done by the one workgroup that
+ *   owns it.
+ * Not served: the gradient of csrVal, half features, [nnz, heads] values,
+ *   column-major operands, BSR, several GPUs. */
+typedef enum { SPMM_REDUCE_MAX = 0, SPMM_REDUCE_MIN = 1 } spmm_reduce_t;
+spmm_status_t spmm_csrmm_reduce_host_f32(spmm_reduce_t op, int m, int n, int k, int nnz,
+                                         const int* csrRowPtr, const int* csrColInd,
+                                         const float* csrVal, spmm_index_base_t base,
+                                         const float* B, int ldb, float* C, int ldc, int* arg,
+                                         int ldarg);
+spmm_status_t spmm_csrmm_reduce_f32(spmm_handle_t handle, spmm_reduce_t op, int m, int n, int k,
+                                    int nnz, const int* csrRowPtr, const int* csrColInd,
+                                    const float* csrVal, spmm_index_base_t base, const float* B,
+                                    int ldb, float* C, int ldc, int* arg, int ldarg);
+spmm_status_t spmm_csrmm_reduce_bwd_host_f32(int k, int n, int m, int nnz, const int* tRowPtr,
+                                             const int* tColInd, const int* perm,
+                                             const float* csrVal, spmm_index_base_t base,
+                                             const float* dC, int lddc, const int* arg,
+                                             int ldarg, float* dB, int lddb);
+spmm_status_t spmm_csrmm_reduce_bwd_f32(spmm_handle_t handle, int k, int n, int m, int nnz,
+                                        const int* tRowPtr, const int* tColInd, const int* perm,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const float* dC, int lddc, const int* arg, int ldarg,
+                                        float* dB, int lddb);
 
 /* cusparseXcoo2csr (csrmm.cu:148-149): csrRowPtr[m+1] of a COO whose row
  * indices cooRowInd[nnz] are sorted ascending (device pointers, handle's

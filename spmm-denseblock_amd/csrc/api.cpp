@@ -369,6 +369,42 @@ spmm_status_t spmm_csrmm_heads_bf16(spmm_handle_t handle, int m, int d, int k, i
                           base, B, ldb, beta, C, ldc);
 }
 
+// The max / min reducers: spmm_csrmm_ex_f32's checks in its order. An nnz of
+// 0 is no quick return: the outputs are overwritten, so the kernel fills them.
+spmm_status_t spmm_csrmm_reduce_f32(spmm_handle_t handle, spmm_reduce_t op, int m, int n, int k,
+                                    int nnz, const int* csrRowPtr, const int* csrColInd,
+                                    const float* csrVal, spmm_index_base_t base, const float* B,
+                                    int ldb, float* C, int ldc, int* arg, int ldarg) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (op != SPMM_REDUCE_MAX && op != SPMM_REDUCE_MIN) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && !csrColInd))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < n || ldc < n || (arg && ldarg < n)) return SPMM_STATUS_INVALID_VALUE;
+  return launch_csrmm_reduce(handle, op == SPMM_REDUCE_MIN, m, n, nnz, csrRowPtr, csrColInd,
+                             csrVal, (int)base, B, ldb, C, ldc, arg, ldarg);
+}
+
+spmm_status_t spmm_csrmm_reduce_bwd_f32(spmm_handle_t handle, int k, int n, int m, int nnz,
+                                        const int* tRowPtr, const int* tColInd, const int* perm,
+                                        const float* csrVal, spmm_index_base_t base,
+                                        const float* dC, int lddc, const int* arg, int ldarg,
+                                        float* dB, int lddb) {
+  if (!handle) return SPMM_STATUS_NOT_INITIALIZED;
+  if (k < 0 || n < 0 || m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (k == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  if (!tRowPtr || !dB || (nnz > 0 && (!tColInd || !perm || !dC || !arg)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (lddc < n || ldarg < n || lddb < n) return SPMM_STATUS_INVALID_VALUE;
+  return launch_csrmm_reduce_bwd(handle, k, n, nnz, tRowPtr, tColInd, perm, csrVal, (int)base,
+                                 dC, lddc, arg, ldarg, dB, lddb);
+}
+
 spmm_status_t spmm_csr_hot_analysis(spmm_handle_t handle, int n, int k, int nnz,
                                     const int* csrColInd, spmm_index_base_t base,
                                     long long hotBytes, int* csrColIndHot) {

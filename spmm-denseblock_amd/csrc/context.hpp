@@ -221,6 +221,17 @@ spmm_status_t launch_csrmm_heads_half(spmm_context* ctx, bool bf16, int m, int d
                                       const float* val, int base, const uint16_t* B, int ldb,
                                       float alpha, float beta, float* C, int ldc);
 
+// spmm_csrmm_reduce_f32 and spmm_csrmm_reduce_bwd_f32 (reduce_kernels.hip): one launch each,
+// no workspace. val and (forward) arg may be null; kt: the rows of A^T.
+spmm_status_t launch_csrmm_reduce(spmm_context* ctx, bool is_min, int m, int n, int nnz,
+                                  const int* rowptr, const int* colind, const float* val,
+                                  int base, const float* B, int ldb, float* C, int ldc, int* arg,
+                                  int ldarg);
+spmm_status_t launch_csrmm_reduce_bwd(spmm_context* ctx, int kt, int n, int nnz,
+                                      const int* trowptr, const int* tcol, const int* perm,
+                                      const float* val, int base, const float* dC, int lddc,
+                                      const int* arg, int ldarg, float* dB, int lddb);
+
 spmm_status_t launch_transpose16(spmm_context* ctx, int rows, int cols, const uint16_t* src,
                                  int ld_src, uint16_t* dst, int ld_dst);
 spmm_status_t launch_transpose(spmm_context* ctx, int rows, int cols, const float* src,

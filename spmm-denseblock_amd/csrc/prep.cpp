@@ -619,6 +619,125 @@ spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads,
   return SPMM_STATUS_SUCCESS;
 }
 
+// The max / min reducers of the CSR product and their backward on the host:
+// the written rules in executable form; the device entries equal them bit for bit. Workers
+// take equal shares of the rows; an output depends on its own row alone.
+//
+// Forward: the terms of a row are walked in ascending position; a term takes over when the
+// holder is not a NaN and the term is a NaN or strictly greater (less) under the IEEE
+// comparison, so the winner is the lowest NaN position if there is one and otherwise the
+// lowest position of the greatest (least) term. C holds the winner's own bits.
+spmm_status_t spmm_csrmm_reduce_host_f32(spmm_reduce_t op, int m, int n, int k, int nnz,
+                                         const int* csrRowPtr, const int* csrColInd,
+                                         const float* csrVal, spmm_index_base_t base,
+                                         const float* B, int ldb, float* C, int ldc, int* arg,
+                                         int ldarg) {
+  if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (op != SPMM_REDUCE_MAX && op != SPMM_REDUCE_MIN) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (m == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  if (!csrRowPtr || !C || (k > 0 && !B) || (nnz > 0 && !csrColInd))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (ldb < n || ldc < n || (arg && ldarg < n)) return SPMM_STATUS_INVALID_VALUE;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)csrRowPtr[0] - ba, p1 = (int64_t)csrRowPtr[m] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (csrRowPtr[r + 1] < csrRowPtr[r]) ok = false;
+  });
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    for (int64_t p = p0 + lo; p < p0 + hi; ++p)
+      if (csrColInd[p] - ba < 0 || csrColInd[p] - ba >= k) ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  const bool mn = op == SPMM_REDUCE_MIN;
+  spmm_host::parallel_for(m, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)csrRowPtr[r] - ba, b = (int64_t)csrRowPtr[r + 1] - ba;
+      float* cr = C + r * ldc;
+      int* wr = arg ? arg + r * ldarg : nullptr;
+      if (a == b)
+        for (int c = 0; c < n; ++c) {
+          cr[c] = 0.f;
+          if (wr) wr[c] = -1;
+        }
+      for (int64_t p = a; p < b; ++p) {
+        const float* br = B + (int64_t)(csrColInd[p] - ba) * ldb;
+        for (int c = 0; c < n; ++c) {
+          float t = br[c];
+          if (csrVal) {
+            volatile float prod = csrVal[p] * br[c];  // one rounding, nothing fused
+            t = prod;
+          }
+          const float v = cr[c];
+          const bool better = mn ? !(t >= v) : !(t <= v);
+          if (p == a || (v == v && better)) {
+            cr[c] = t;
+            if (wr) wr[c] = (int)p;
+          }
+        }
+      }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
+// Backward: row c of A^T, positions [ta, tb), column j: the selected positions
+// (arg[i, j] == perm[q], i = tColInd[q] - base) enter fma(v, dC[i, j], acc) chains under the
+// product's piece rule counted over all positions: pieces of max(128, ceil(L / 64)), each
+// from +0, added left to right from -0; an empty row is +0. arg is compared, never used as
+// an index.
+spmm_status_t spmm_csrmm_reduce_bwd_host_f32(int k, int n, int m, int nnz, const int* tRowPtr,
+                                             const int* tColInd, const int* perm,
+                                             const float* csrVal, spmm_index_base_t base,
+                                             const float* dC, int lddc, const int* arg,
+                                             int ldarg, float* dB, int lddb) {
+  if (k < 0 || n < 0 || m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
+  if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
+    return SPMM_STATUS_INVALID_VALUE;
+  if (k == 0 || n == 0) return SPMM_STATUS_SUCCESS;
+  if (!tRowPtr || !dB || (nnz > 0 && (!tColInd || !perm || !dC || !arg)))
+    return SPMM_STATUS_INVALID_VALUE;
+  if (lddc < n || ldarg < n || lddb < n) return SPMM_STATUS_INVALID_VALUE;
+  const int ba = (int)base;
+  const int64_t p0 = (int64_t)tRowPtr[0] - ba, p1 = (int64_t)tRowPtr[k] - ba;
+  if (p0 < 0 || p1 < p0 || p1 > nnz) return SPMM_STATUS_INVALID_VALUE;
+  std::atomic<bool> ok{true};
+  spmm_host::parallel_for(k, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r)
+      if (tRowPtr[r + 1] < tRowPtr[r]) ok = false;
+  });
+  spmm_host::parallel_for(p1 - p0, [&](int64_t lo, int64_t hi) {
+    for (int64_t q = p0 + lo; q < p0 + hi; ++q)
+      if (tColInd[q] - ba < 0 || tColInd[q] - ba >= m || perm[q] < 0 || perm[q] >= nnz)
+        ok = false;
+  });
+  if (!ok) return SPMM_STATUS_INVALID_VALUE;
+  spmm_host::parallel_for(k, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t a = (int64_t)tRowPtr[r] - ba, b = (int64_t)tRowPtr[r + 1] - ba;
+      const int64_t T = std::max<int64_t>(128, (b - a + 63) / 64);
+      for (int c = 0; c < n; ++c) {
+        volatile float x = b > a ? -0.f : 0.f;  // no reassociation of the piece sums
+        for (int64_t s = a; s < b; s += T) {
+          float acc = 0.f;
+          for (int64_t q = s; q < std::min(s + T, b); ++q) {
+            const int64_t i = tColInd[q] - ba;
+            if (arg[i * ldarg + c] != perm[q]) continue;
+            acc = __builtin_fmaf(csrVal ? csrVal[perm[q]] : 1.f, dC[i * lddc + c], acc);
+          }
+          x = x + acc;
+        }
+        dB[r * lddb + c] = x;
+      }
+    }
+  });
+  return SPMM_STATUS_SUCCESS;
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------

@@ -30,6 +30,7 @@ DIRECTION_ROW, DIRECTION_COLUMN = 0, 1
 OPERATION_NON_TRANSPOSE, OPERATION_TRANSPOSE = 0, 1
 ORDER_ROW, ORDER_COL = 0, 1
 INDEX_BASE_ZERO, INDEX_BASE_ONE = 0, 1
+REDUCE_MAX, REDUCE_MIN = 0, 1
 CSR_NT_STREAMS = 1
 CSR_SEQUENTIAL_ROWS = 2
 HYBRID_FUSED = 1
@@ -226,6 +227,14 @@ _PROTOS = {
                                           c_int, _P, c_int, c_float, _P, c_int]),
     "spmm_csrmm_heads_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
                                      c_int, _P, c_int, c_float, _P, c_int]),
+    "spmm_csrmm_reduce_host_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int,
+                                           _P, c_int, _P, c_int, _P, c_int]),
+    "spmm_csrmm_reduce_f32": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int,
+                                      _P, c_int, _P, c_int, _P, c_int]),
+    "spmm_csrmm_reduce_bwd_host_f32": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int,
+                                               _P, c_int, _P, c_int, _P, c_int]),
+    "spmm_csrmm_reduce_bwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int,
+                                          _P, c_int, _P, c_int, _P, c_int]),
     "spmm_xcoo2csr": (c_int, [_P, _P, c_int, c_int, _P, c_int]),
     # spmm_multi.h
     "spmm_multi_create": (c_int, [POINTER(c_void_p), c_int, _P]),

@@ -32,6 +32,12 @@ launch per op (ops.*_heads): features [rows, heads, d], edge values [nnz, heads]
 H may be float16 or bfloat16 there (ops.*_heads on half features): the logits, the softmax
 and every edge gradient stay float32, the kernels accumulate in float32, and a result that
 takes the features' place (H1, H.grad) is cast to H's type once, round to nearest even.
+
+spmm_reduce is the product with max or min in place of the sum (GraphSAGE-pool, PNA): the
+forward keeps the winning positions, the backward is a masked product over A.t() with no
+atomics (ops.csrmm_reduce / ops.csrmm_reduce_bwd):
+
+    P = spmm_reduce(A, H, "max")                      # [m, n]; H.grad through the winners
 """
 from __future__ import annotations
 
@@ -372,5 +378,64 @@ def sddmm_heads(A: CsrMatrix, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
     return _SddmmHeads.apply(X, Y, A)
 
 
+# ---------------------------------------------------------------- max / min aggregation
+class _SpmmReduce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, B: torch.Tensor, val: torch.Tensor | None, A: CsrMatrix,
+                reduce: str) -> torch.Tensor:
+        ctx.A = A
+        B = B.detach().contiguous()
+        C, arg = ops.csrmm_reduce(A.rowptr, A.colind, val, B, reduce=reduce, m=A.m,
+                                  n=B.shape[1], k=A.k)
+        ctx.save_for_backward(arg, *(() if val is None else (val,)))
+        return C
+
+    @staticmethod
+    def backward(ctx, grad_C: torch.Tensor):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        A = ctx.A
+        arg, *rest = ctx.saved_tensors
+        At = A.t()
+        grad_B = ops.csrmm_reduce_bwd(At.rowptr, At.colind, A.t_perm(), rest[0] if rest else None,
+                                      grad_C.contiguous(), arg, k=A.k, n=arg.shape[1], m=A.m)
+        return grad_B, None, None, None
+
+
+def spmm_reduce(A: CsrMatrix, B: torch.Tensor, reduce: str = "max",
+                val: torch.Tensor | None = None) -> torch.Tensor:
+    """C[i, :] = max (min) over row i's positions p of val[p] * B[col(p), :] on A's pattern
+    (ops.csrmm_reduce; B: [k, n] float32): GraphSAGE-pool / PNA aggregation, DGL's
+    copy_u_max, PyG's aggr="max"; an empty row gives 0.
+
+    val=None: the unweighted aggregation of B's rows; A.val is not read. val: a float32
+    device tensor of nnz edge weights (A.val itself may be passed). It is a constant here:
+    its gradient is a masked sampled product this library does not have, so a val that
+    requires grad is refused, not silently treated as a constant; detach it.
+
+    The forward keeps the winning positions; the backward is ops.csrmm_reduce_bwd on A.t()
+    with A.t_perm(): each grad_C[i, j] goes to the one B row that won, summed over A^T's
+    rows under the product's piece rule. No atomics: two runs give the same bits. The
+    transpose is built once per matrix, on the first backward."""
+    if not isinstance(A, CsrMatrix):
+        raise TypeError("spmm_reduce: A must be a CsrMatrix")
+    if reduce not in ("max", "min"):
+        raise ValueError(f"spmm_reduce: reduce must be 'max' or 'min', got {reduce!r}")
+    _f32_cuda("spmm_reduce", B, "B")
+    if B.dim() != 2 or B.shape[0] != A.k:
+        raise ValueError(f"spmm_reduce: B must be ({A.k}, n), got {tuple(B.shape)}")
+    if val is not None:
+        _f32_cuda("spmm_reduce", val, "val")
+        if val.dim() != 1 or val.numel() != A.colind.numel():
+            raise ValueError(f"spmm_reduce: val must hold the pattern's {A.colind.numel()} "
+                             f"values, got {tuple(val.shape)}")
+        if val.requires_grad:
+            raise ValueError("spmm_reduce: val requires grad, but the gradient of the edge "
+                             "values of a max / min aggregation is not served (a masked "
+                             "sampled product); detach val")
+        val = val.contiguous()
+    return _SpmmReduce.apply(B, val, A, reduce)
+
+
 __all__ = ["CsrMatrix", "spmm", "edge_softmax", "sddmm", "spmm_heads", "edge_softmax_heads",
-           "sddmm_heads"]
+           "sddmm_heads", "spmm_reduce"]

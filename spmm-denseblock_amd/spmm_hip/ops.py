@@ -17,6 +17,10 @@ through the C ABI. The functions mirror the reference's operator interfaces:
   sddmm_heads(...) / edge_softmax_heads(...) / edge_softmax_bwd_heads(...) / csrmm_heads(...)
                       the three ops of graph attention over several heads in one launch
                       each: edge values [nnz, heads], features [rows, heads, d]
+  csrmm_reduce(...) / csrmm_reduce_bwd(...)
+                      the max / min reducers of the CSR product with the winning positions
+                      (DGL's copy_u_max / u_mul_e_max, PyG's aggr="max"), and the gradient
+                      of B from them as a masked product over A^T
 """
 from __future__ import annotations
 
@@ -481,6 +485,119 @@ def csrmm_heads(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor, B
                                 _ptr(colind), _ptr(val), base, _ptr(B), ldb, beta, _ptr(C), ldc),
           entry)
     return C
+
+
+_REDUCE_OPS = {"max": 0, "min": 1}
+
+
+def csrmm_reduce(rowptr: torch.Tensor, colind: torch.Tensor, val: torch.Tensor | None,
+                 B: torch.Tensor, *, reduce: str = "max", m: int | None = None,
+                 n: int | None = None, k: int, ldb: int | None = None,
+                 C: torch.Tensor | None = None, ldc: int | None = None,
+                 arg: torch.Tensor | None = None, ldarg: int | None = None,
+                 return_arg: bool = True, base: int = 0, handle: Handle | None = None):
+    """The max / min reducer of the CSR product (spmm_csrmm_reduce_f32): C[i, j] = max (min)
+    over row i's positions p of val[p] * B[col(p), j] (val None: of B[col(p), j] itself:
+    DGL's copy_u_max, PyG's aggr="max") and arg[i, j] = the winning 0-based position: the
+    lowest NaN position if any, else the lowest position of the greatest (least) term; an
+    empty row gives +0 and -1. B ([k, n]), C ([m, n]) float32 and arg ([m, n]) int32 are
+    row-major with leading dimensions ldb, ldc, ldarg (default n; n defaults to a 2-D B's;
+    C and arg default to new tensors and are overwritten). Returns (C, arg), or C alone
+    with return_arg=False (arg is then neither computed nor written). One kernel: no
+    synchronisation, no workspace, no atomics, capturable; the bits equal
+    prep.csrmm_reduce's whatever the grid."""
+    if reduce not in _REDUCE_OPS:
+        raise ValueError(f"csrmm_reduce: reduce must be 'max' or 'min', got {reduce!r}")
+    for t, dt, nm in ((rowptr, torch.int32, "rowptr"), (colind, torch.int32, "colind"),
+                      (B, torch.float32, "B")):
+        _need(t, dt, nm)
+    if val is not None:
+        _need(val, torch.float32, "val")
+        if val.numel() < colind.numel():
+            raise ValueError("csrmm_reduce: val is shorter than colind")
+    m = rowptr.numel() - 1 if m is None else m
+    if n is None:
+        if B.dim() != 2:
+            raise ValueError("csrmm_reduce: n is needed when B is not a 2-D tensor")
+        n = B.shape[1]
+    ldb = n if ldb is None else ldb
+    ldc = n if ldc is None else ldc
+    ldarg = n if ldarg is None else ldarg
+    if m < 0 or rowptr.numel() < m + 1:
+        raise ValueError(f"csrmm_reduce: rowptr has {rowptr.numel()} entries, needs m + 1 = {m + 1}")
+    _rows_needed("csrmm_reduce", B, k, ldb, n, "B")
+    if C is None:
+        if ldc != n:
+            raise ValueError("csrmm_reduce: a padded ldc needs a C of the caller's")
+        C = torch.empty((m, n), dtype=torch.float32, device=B.device)
+    _need(C, torch.float32, "C")
+    _rows_needed("csrmm_reduce", C, m, ldc, n, "C")
+    if return_arg:
+        if arg is None:
+            if ldarg != n:
+                raise ValueError("csrmm_reduce: a padded ldarg needs an arg of the caller's")
+            arg = torch.empty((m, n), dtype=torch.int32, device=B.device)
+        _need(arg, torch.int32, "arg")
+        _rows_needed("csrmm_reduce", arg, m, ldarg, n, "arg")
+    elif arg is not None:
+        raise ValueError("csrmm_reduce: arg given with return_arg=False")
+    h = handle or default_handle()
+    check(lib().spmm_csrmm_reduce_f32(h.raw, _REDUCE_OPS[reduce], m, n, k, colind.numel(),
+                                      _ptr(rowptr), _ptr(colind), _ptr(val), base, _ptr(B), ldb,
+                                      _ptr(C), ldc, _ptr(arg), ldarg), "spmm_csrmm_reduce_f32")
+    return (C, arg) if return_arg else C
+
+
+def csrmm_reduce_bwd(trowptr: torch.Tensor, tcolind: torch.Tensor, perm: torch.Tensor,
+                     val: torch.Tensor | None, dC: torch.Tensor, arg: torch.Tensor, *,
+                     k: int | None = None, n: int | None = None, m: int,
+                     lddc: int | None = None, ldarg: int | None = None,
+                     dB: torch.Tensor | None = None, lddb: int | None = None, base: int = 0,
+                     handle: Handle | None = None) -> torch.Tensor:
+    """The backward of csrmm_reduce for B (spmm_csrmm_reduce_bwd_f32), a masked product over
+    A^T with no atomics: dB[c, j] = the sum over the positions q of row c of A^T (trowptr,
+    tcolind: k rows; csr2csc's output) with arg[i, j] == perm[q], i = tcolind[q], of
+    val[perm[q]] * dC[i, j] (val None: of dC[i, j]), under the piece rule of the CSR product
+    counted over all of the row's positions. perm: csr2csc's (return_perm=True); val in A's
+    order. dC ([m, n]) float32, arg ([m, n]) int32, dB ([k, n]; default a new tensor,
+    overwritten) with leading dimensions lddc, ldarg, lddb (default n; n defaults to a 2-D
+    dC's). arg is only compared, never used as an index. One kernel, capturable; the bits
+    equal prep.csrmm_reduce_bwd's."""
+    for t, dt, nm in ((trowptr, torch.int32, "trowptr"), (tcolind, torch.int32, "tcolind"),
+                      (perm, torch.int32, "perm"), (dC, torch.float32, "dC"),
+                      (arg, torch.int32, "arg")):
+        _need(t, dt, nm)
+    if val is not None:
+        _need(val, torch.float32, "val")
+        if val.numel() < tcolind.numel():
+            raise ValueError("csrmm_reduce_bwd: val is shorter than tcolind")
+    if perm.numel() < tcolind.numel():
+        raise ValueError("csrmm_reduce_bwd: perm is shorter than tcolind")
+    k = trowptr.numel() - 1 if k is None else k
+    if n is None:
+        if dC.dim() != 2:
+            raise ValueError("csrmm_reduce_bwd: n is needed when dC is not a 2-D tensor")
+        n = dC.shape[1]
+    lddc = n if lddc is None else lddc
+    ldarg = n if ldarg is None else ldarg
+    lddb = n if lddb is None else lddb
+    if k < 0 or trowptr.numel() < k + 1:
+        raise ValueError(f"csrmm_reduce_bwd: trowptr has {trowptr.numel()} entries, needs k + 1 = "
+                         f"{k + 1}")
+    _rows_needed("csrmm_reduce_bwd", dC, m, lddc, n, "dC")
+    _rows_needed("csrmm_reduce_bwd", arg, m, ldarg, n, "arg")
+    if dB is None:
+        if lddb != n:
+            raise ValueError("csrmm_reduce_bwd: a padded lddb needs a dB of the caller's")
+        dB = torch.empty((k, n), dtype=torch.float32, device=dC.device)
+    _need(dB, torch.float32, "dB")
+    _rows_needed("csrmm_reduce_bwd", dB, k, lddb, n, "dB")
+    h = handle or default_handle()
+    check(lib().spmm_csrmm_reduce_bwd_f32(h.raw, k, n, m, tcolind.numel(), _ptr(trowptr),
+                                          _ptr(tcolind), _ptr(perm), _ptr(val), base, _ptr(dC),
+                                          lddc, _ptr(arg), ldarg, _ptr(dB), lddb),
+          "spmm_csrmm_reduce_bwd_f32")
+    return dB
 
 
 def csr_hot_analysis(colind: torch.Tensor, *, n: int, k: int, base: int = 0,

@@ -4,6 +4,7 @@ Thin wrappers over the C ABI of libspmm_hip.so:
   csr2bsr / bsr2csr / csr2csc / sddmm / calculate_nnzb / partition_rows   (include/spmm_hip.h)
   edge_softmax / edge_softmax_bwd                                        (include/spmm_hip.h)
   sddmm_heads / edge_softmax_heads / edge_softmax_bwd_heads / csrmm_heads (include/spmm_hip.h)
+  csrmm_reduce / csrmm_reduce_bwd (max / min aggregation)                (include/spmm_hip.h)
   rng_seed / random_array / random_csr / random_bsr /
   load_csr / dump_csr / load_graph / save_csr_bin / load_csr_bin / load_csr_cached /
   powerlaw_csr / community_csr                                  (include/spmm_host.h)
@@ -308,6 +309,94 @@ def csrmm_heads(m: int, d: int, k: int, heads: int, rowptr, colind, val, B, *,
     check(getattr(lib(), entry)(m, d, k, colind.size, heads, alpha, _p(rowptr), _p(colind),
                                 _p(val), base, _p(B), ldb, beta, _p(C), ldc), entry)
     return C
+
+
+_REDUCE_OPS = {"max": 0, "min": 1}
+
+
+def _reduce_op(where: str, reduce) -> int:
+    if reduce not in _REDUCE_OPS:
+        raise ValueError(f"{where}: reduce must be 'max' or 'min', got {reduce!r}")
+    return _REDUCE_OPS[reduce]
+
+
+def _i32c(where: str, nm: str, a, size: int | None = None) -> None:
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or not a.flags.c_contiguous:
+        raise TypeError(f"{where}: {nm} must be a C-contiguous int32 array")
+    if size is not None and a.size < size:
+        raise ValueError(f"{where}: {nm} holds {a.size} entries, needs {size}")
+
+
+def _dense_out(where: str, nm: str, a, rows: int, ld: int, n: int, dtype, fill):
+    """The output `a` checked, or a new one of `rows` rows filled with `fill` (2-D when the
+    rows are not padded)."""
+    size = (rows - 1) * ld + n if rows > 0 and ld >= n else 0
+    if a is None:
+        a = np.full(size, fill, dtype=dtype)
+        return a.reshape(rows, n) if ld == n and rows > 0 else a
+    (_f32c if dtype == np.float32 else _i32c)(where, nm, a, size)
+    return a
+
+
+def csrmm_reduce(m: int, n: int, k: int, rowptr, colind, val, B, *, reduce: str = "max",
+                 ldb: int | None = None, C=None, ldc: int | None = None, arg=None,
+                 ldarg: int | None = None, return_arg: bool = True, base: int = 0):
+    """spmm_csrmm_reduce_host_f32: C[i, j] = max (min) over row i's positions p of
+    val[p] * B[col(p), j] (val None: of B[col(p), j] itself) and arg[i, j] = the winning
+    0-based position: the lowest NaN position if any, else the lowest position of the
+    greatest (least) term; an empty row gives +0 and -1 (the bits of ops.csrmm_reduce). B:
+    float32 with leading dimension ldb (default n); C float32 / arg int32 with ldc / ldarg
+    (default n; new arrays by default). Returns (C, arg), or C with return_arg=False (arg is
+    then not computed)."""
+    op = _reduce_op("csrmm_reduce", reduce)
+    rowptr, colind = _i32(rowptr), _i32(colind)
+    if rowptr.size != m + 1:
+        raise ValueError(f"csrmm_reduce: rowptr has {rowptr.size} entries, needs m + 1 = {m + 1}")
+    ldb = n if ldb is None else ldb
+    ldc = n if ldc is None else ldc
+    ldarg = n if ldarg is None else ldarg
+    if val is not None:
+        _f32c("csrmm_reduce", "val", val, colind.size)
+    _f32c("csrmm_reduce", "B", B, (k - 1) * ldb + n if k > 0 and ldb >= n else None)
+    C = _dense_out("csrmm_reduce", "C", C, m, ldc, n, np.float32, 0)
+    if return_arg:
+        arg = _dense_out("csrmm_reduce", "arg", arg, m, ldarg, n, np.int32, -1)
+    elif arg is not None:
+        raise ValueError("csrmm_reduce: arg given with return_arg=False")
+    check(lib().spmm_csrmm_reduce_host_f32(op, m, n, k, colind.size, _p(rowptr), _p(colind),
+                                           _p(val), base, _p(B), ldb, _p(C), ldc, _p(arg),
+                                           ldarg), "spmm_csrmm_reduce_host_f32")
+    return (C, arg) if return_arg else C
+
+
+def csrmm_reduce_bwd(k: int, n: int, m: int, trowptr, tcolind, perm, val, dC, arg, *,
+                     lddc: int | None = None, ldarg: int | None = None, dB=None,
+                     lddb: int | None = None, base: int = 0) -> np.ndarray:
+    """spmm_csrmm_reduce_bwd_host_f32: dB[c, j] = the sum over the positions q of row c of
+    A^T (trowptr, tcolind: k rows) with arg[i, j] == perm[q], i = tcolind[q], of
+    val[perm[q]] * dC[i, j] (val None: of dC[i, j]) under the product's piece rule counted
+    over all of the row's positions (the bits of ops.csrmm_reduce_bwd). perm: csr2csc's;
+    val in A's order. dC float32 [m, lddc], arg int32 [m, ldarg], dB float32 [k, lddb]
+    (default a new array; returned). arg is only compared, never used as an index."""
+    trowptr, tcolind, perm = _i32(trowptr), _i32(tcolind), _i32(perm)
+    if trowptr.size != k + 1:
+        raise ValueError(f"csrmm_reduce_bwd: trowptr has {trowptr.size} entries, needs k + 1 = "
+                         f"{k + 1}")
+    if perm.size != tcolind.size:
+        raise ValueError("csrmm_reduce_bwd: perm and tcolind differ in length")
+    lddc = n if lddc is None else lddc
+    ldarg = n if ldarg is None else ldarg
+    lddb = n if lddb is None else lddb
+    if val is not None:
+        _f32c("csrmm_reduce_bwd", "val", val, tcolind.size)
+    _f32c("csrmm_reduce_bwd", "dC", dC, (m - 1) * lddc + n if m > 0 and lddc >= n else None)
+    _i32c("csrmm_reduce_bwd", "arg", arg, (m - 1) * ldarg + n if m > 0 and ldarg >= n else None)
+    dB = _dense_out("csrmm_reduce_bwd", "dB", dB, k, lddb, n, np.float32, 0)
+    check(lib().spmm_csrmm_reduce_bwd_host_f32(k, n, m, tcolind.size, _p(trowptr), _p(tcolind),
+                                               _p(perm), _p(val), base, _p(dC), lddc, _p(arg),
+                                               ldarg, _p(dB), lddb),
+          "spmm_csrmm_reduce_bwd_host_f32")
+    return dB
 
 
 def calculate_nnzb(n: int, rowptr, colind, bs: int) -> int:
