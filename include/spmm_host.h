@@ -12,6 +12,17 @@
  *   loadGraphFromFile                 load_data.cc:167-184 ("n nnz" + edge list)
  * (text parsed and written by worker threads, host_io.cpp; same results as the
  * reference's iostream loops on well-formed files, -1 on malformed ones)
+ * What a loader returns is a CSR matrix or nothing. Every loader refuses, with -1 and the
+ * out-pointers left as they were: a missing or short file, a token that is no integer or
+ * past int range, a negative size, fewer tokens than the header says, and a header that
+ * asks for more than its file can hold (c tokens take at least 2 c - 1 bytes; the binary
+ * cache's arrays their exact sizes), which is checked before anything is sized from it.
+ *   spmm_host_load_graph: a source or a destination outside [0, n).
+ *   spmm_host_load_csr, _csr_bin, _csr_cached: rowptr[0] != 0, a decreasing row pointer,
+ *     rowptr[n] != nnz, a negative column. The files carry no column count, so the upper
+ *     bound on the columns stays the caller's concern: check it before the arrays go to
+ *     an entry that does not validate (the device products do not).
+ * No C++ exception leaves these functions: an allocation failure is -1.
  * All of them draw from ONE process-wide generator, as the reference's
  * `static std::mt19937_64 gen(1234)` (load_data.cc:12) does, so call order
  * matters exactly as it does there. Arrays returned through T** are

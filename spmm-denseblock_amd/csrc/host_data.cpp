@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <random>
@@ -34,6 +35,26 @@ T* to_malloc(const std::vector<T>& v) {
   T* p = static_cast<T*>(std::malloc(std::max<size_t>(1, v.size()) * sizeof(T)));
   if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
   return p;
+}
+
+// A malloc'ed array that is freed on every way out, an exception's included, until it is
+// released to the caller.
+struct Freer {
+  void operator()(void* p) const { std::free(p); }
+};
+using OwnedInts = std::unique_ptr<int[], Freer>;
+
+// Hands two malloc'ed arrays to the caller, or frees both when either allocation failed.
+template <typename A, typename B>
+bool hand_over(A* a, A** a_out, B* b, B** b_out) {
+  if (!a || !b) {
+    std::free(a);
+    std::free(b);
+    return false;
+  }
+  *a_out = a;
+  *b_out = b;
+  return true;
 }
 
 inline uint64_t splitmix64(uint64_t x) {
@@ -102,20 +123,22 @@ extern "C" {
 
 void spmm_host_free(void* p) { std::free(p); }
 
-void spmm_host_rng_seed(uint64_t seed) {
+void spmm_host_rng_seed(uint64_t seed) try {
   std::lock_guard<std::mutex> lk(gen_mu());
   shared_gen().seed(seed);
+} catch (...) {  // no exception leaves the C ABI
 }
 
-void spmm_host_random_array(int64_t n, float minVal, float maxVal, float* out) {
+void spmm_host_random_array(int64_t n, float minVal, float maxVal, float* out) try {
   std::lock_guard<std::mutex> lk(gen_mu());
   std::uniform_real_distribution<float> dist(minVal, maxVal);
   auto& g = shared_gen();
   for (int64_t i = 0; i < n; ++i) out[i] = dist(g);
+} catch (...) {  // no exception leaves the C ABI
 }
 
 int64_t spmm_host_random_csr(int m, int n, float p, float minVal, float maxVal, int* rowptr,
-                             int** colind, float** val) {
+                             int** colind, float** val) try {
   if (m < 0 || n < 0 || !rowptr || !colind || !val) return -1;
   std::lock_guard<std::mutex> lk(gen_mu());
   std::uniform_real_distribution<float> flip(0, 1), dist(minVal, maxVal);
@@ -134,13 +157,13 @@ int64_t spmm_host_random_csr(int m, int n, float p, float minVal, float maxVal, 
     }
     rowptr[i] = (int)cnt;
   }
-  *colind = to_malloc(idx);
-  *val = to_malloc(vals);
-  return cnt;
+  return hand_over(to_malloc(idx), colind, to_malloc(vals), val) ? cnt : -1;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int64_t spmm_host_random_bsr(int mb, int nb, int blockDim, float p, float minVal, float maxVal,
-                             int* rowptr, int** colind, float** val) {
+                             int* rowptr, int** colind, float** val) try {
   if (mb < 0 || nb < 0 || blockDim <= 0 || !rowptr || !colind || !val) return -1;
   std::lock_guard<std::mutex> lk(gen_mu());
   std::uniform_real_distribution<float> flip(0, 1), dist(minVal, maxVal);
@@ -160,15 +183,15 @@ int64_t spmm_host_random_bsr(int mb, int nb, int blockDim, float p, float minVal
     }
     rowptr[i] = (int)cnt;
   }
-  *colind = to_malloc(idx);
-  *val = to_malloc(vals);
-  return cnt;
+  return hand_over(to_malloc(idx), colind, to_malloc(vals), val) ? cnt : -1;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 // spmm_host_dump_csr / spmm_host_load_csr / spmm_host_load_graph: host_io.cpp.
 
 int spmm_host_gen_powerlaw_csr(int n, int64_t nnz_target, int max_deg, double gamma,
-                               uint64_t seed, int** rowptr_out, int** colind_out) {
+                               uint64_t seed, int** rowptr_out, int** colind_out) try {
   if (n <= 0 || nnz_target < 0 || max_deg <= 0 || gamma <= 1.0 || !rowptr_out || !colind_out)
     return -1;
   if ((double)max_deg > 0.5 * n || nnz_target > (int64_t)n * (n / 2) || nnz_target > INT32_MAX)
@@ -223,7 +246,9 @@ int spmm_host_gen_powerlaw_csr(int n, int64_t nnz_target, int max_deg, double ga
   for (int i = 0; i < n; ++i) inv[perm[i]] = i;
   std::vector<int> rp(n + 1, 0);
   for (int r = 0; r < n; ++r) rp[r + 1] = rp[r] + deg[inv[r]];
-  int* ci = static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max<int64_t>(1, nnz_target)));
+  OwnedInts owned(
+      static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max<int64_t>(1, nnz_target))));
+  int* const ci = owned.get();
   if (!ci) return -1;
   parallel_for(n, [&](int64_t lo_r, int64_t hi_r) {
     std::vector<int> cols;
@@ -236,14 +261,18 @@ int spmm_host_gen_powerlaw_csr(int n, int64_t nnz_target, int max_deg, double ga
       std::copy(cols.begin(), cols.end(), ci + rp[r]);
     }
   });
-  *rowptr_out = to_malloc(rp);
-  *colind_out = ci;
+  int* rpo = to_malloc(rp);
+  if (!rpo) return -1;
+  *rowptr_out = rpo;
+  *colind_out = owned.release();
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_host_gen_community_csr(int n, double avg_deg, int cmin, int cmax, double p_in,
                                 uint64_t seed, int** rowptr_out, int** colind_out,
-                                int64_t* nnz_out) {
+                                int64_t* nnz_out) try {
   if (n <= 0 || avg_deg < 0 || cmin <= 0 || cmax < cmin || p_in < 0 || p_in > 1 ||
       !rowptr_out || !colind_out || !nnz_out)
     return -1;
@@ -283,7 +312,8 @@ int spmm_host_gen_community_csr(int n, double avg_deg, int cmin, int cmax, doubl
   std::vector<int> rp(n + 1, 0);
   for (int r = 0; r < n; ++r) rp[r + 1] = rp[r] + (int)rows[r].size();
   const int64_t nnz = rp[n];
-  int* ci = static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max<int64_t>(1, nnz)));
+  OwnedInts owned(static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max<int64_t>(1, nnz))));
+  int* const ci = owned.get();
   if (!ci) return -1;
   parallel_for(n, [&](int64_t lo, int64_t hi) {
     for (int64_t r = lo; r < hi; ++r) {
@@ -291,10 +321,14 @@ int spmm_host_gen_community_csr(int n, double avg_deg, int cmin, int cmax, doubl
       std::vector<int>().swap(rows[r]);
     }
   });
-  *rowptr_out = to_malloc(rp);
-  *colind_out = ci;
+  int* rpo = to_malloc(rp);
+  if (!rpo) return -1;
+  *rowptr_out = rpo;
+  *colind_out = owned.release();
   *nnz_out = nnz;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -91,18 +92,10 @@ int64_t parse_ints(const char* buf, size_t begin, size_t end, T* out, int64_t ex
       i = j;
     }
   };
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(count, t);
-    for (auto& x : th) x.join();
-  }
+  spmm_host::run_workers(nt, count);
   for (int t = 0; t < nt; ++t) cnt[t + 1] += cnt[t];
   if (cnt[nt] < expect) return -1;
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(parse, t, cnt[t]);
-    for (auto& x : th) x.join();
-  }
+  spmm_host::run_workers(nt, [&](int t) { parse(t, cnt[t]); });
   return bad ? -1 : cnt[nt];
 }
 
@@ -190,6 +183,25 @@ struct BinHeader {
 };
 constexpr char kMagic[8] = {'S', 'P', 'M', 'M', 'C', 'S', 'R', '1'};
 
+// malloc'ed arrays that are freed on every way out until they are handed to the caller.
+struct Freer {
+  void operator()(void* p) const { std::free(p); }
+};
+template <typename T>
+using Owned = std::unique_ptr<T[], Freer>;
+template <typename T>
+Owned<T> owned_alloc(int64_t count) {
+  return Owned<T>(static_cast<T*>(std::malloc(sizeof(T) * (size_t)std::max<int64_t>(1, count))));
+}
+
+// What every CSR loader checks before it returns arrays (include/spmm_host.h):
+// rowptr[0] == 0, no decreasing row pointer, rowptr[n] == nnz, no negative column. The
+// files carry no column count, so the columns have no upper bound here.
+bool loaded_csr_ok(int64_t n, int64_t nnz, const int* rp, const int* ci) {
+  if (rp[0] != 0 || rp[n] != nnz) return false;
+  return spmm_host::valid_csr((int)n, rp, ci, (int64_t)INT32_MAX + 1);
+}
+
 int64_t mtime_ns(const std::string& path) {
   struct stat st;
   if (stat(path.c_str(), &st) != 0) return -1;
@@ -201,7 +213,7 @@ int64_t mtime_ns(const std::string& path) {
 extern "C" {
 
 int spmm_host_dump_csr(const char* prefix, int n, int64_t nnz, const int* rowptr,
-                       const int* colind) {
+                       const int* colind) try {
   if (!prefix || n < 0 || !rowptr || nnz < 0 || (nnz > 0 && !colind)) return -1;
   const std::string p(prefix);
   FILE* f1 = std::fopen((p + "_indptr.txt").c_str(), "wb");
@@ -216,9 +228,11 @@ int spmm_host_dump_csr(const char* prefix, int n, int64_t nnz, const int* rowptr
   if (f1 && std::fclose(f1) != 0) ok = false;
   if (f2 && std::fclose(f2) != 0) ok = false;
   return ok ? 0 : -1;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_host_load_csr(const char* prefix, int** rowptr, int** colind, int* n, int64_t* nnz) {
+int spmm_host_load_csr(const char* prefix, int** rowptr, int** colind, int* n, int64_t* nnz) try {
   if (!prefix || !rowptr || !colind || !n || !nnz) return -1;
   const std::string p(prefix);
   std::vector<char> b1, b2;
@@ -227,23 +241,26 @@ int spmm_host_load_csr(const char* prefix, int** rowptr, int** colind, int* n, i
   size_t a1 = 0, a2 = 0;
   if (!next_token(b1, 0, np1, a1) || np1 < 1 || np1 - 1 > INT32_MAX) return -1;
   if (!next_token(b2, 0, z, a2) || z < 0) return -1;
-  int* rp = static_cast<int*>(std::malloc(sizeof(int) * (size_t)np1));
-  int* ci = static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max(1LL, z)));
-  if (!rp || !ci || parse_ints(b1.data(), a1, b1.size(), rp, np1) < 0 ||
-      parse_ints(b2.data(), a2, b2.size(), ci, z) < 0) {
-    std::free(rp);
-    std::free(ci);
+  // c tokens and their separators take at least 2 c - 1 bytes: a header that asks for
+  // more than its file can hold is refused before anything is sized from it.
+  if (2 * np1 - 1 > (long long)(b1.size() - a1) || 2 * z - 1 > (long long)(b2.size() - a2))
     return -1;
-  }
-  *rowptr = rp;
-  *colind = ci;
+  Owned<int> rp = owned_alloc<int>(np1), ci = owned_alloc<int>(z);
+  if (!rp || !ci || parse_ints(b1.data(), a1, b1.size(), rp.get(), np1) < 0 ||
+      parse_ints(b2.data(), a2, b2.size(), ci.get(), z) < 0)
+    return -1;
+  if (!loaded_csr_ok(np1 - 1, z, rp.get(), ci.get())) return -1;
+  *rowptr = rp.release();
+  *colind = ci.release();
   *n = (int)(np1 - 1);
   *nnz = z;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_host_load_graph(const char* filename, int** rowptr, int** colind, int* n_out,
-                         int64_t* nnz_out) {
+                         int64_t* nnz_out) try {
   if (!filename || !rowptr || !colind || !n_out || !nnz_out) return -1;
   std::vector<char> buf;
   if (!read_file(filename, buf)) return -1;
@@ -252,6 +269,9 @@ int spmm_host_load_graph(const char* filename, int** rowptr, int** colind, int* 
   if (!next_token(buf, 0, hdr[0], a) || !next_token(buf, a, hdr[1], pos)) return -1;
   const long long n = hdr[0], nnz = hdr[1];
   if (n < 0 || n > INT32_MAX || nnz < 0 || nnz > INT32_MAX) return -1;
+  // 2 nnz tokens and their separators take at least 4 nnz - 1 bytes: a header that asks
+  // for more edges than the file can hold is refused before anything is sized from it.
+  if (4 * nnz - 1 > (long long)(buf.size() - pos)) return -1;
   std::vector<int> ed((size_t)2 * nnz);
   if (parse_ints(buf.data(), pos, buf.size(), ed.data(), 2 * nnz) < 0) return -1;
   buf.clear();
@@ -260,8 +280,8 @@ int spmm_host_load_graph(const char* filename, int** rowptr, int** colind, int* 
   // row sorted — the reference's push_back + std::sort per list.
   std::vector<int> rp((size_t)n + 1, 0);
   for (long long e = 0; e < nnz; ++e) {
-    const int x = ed[2 * e];
-    if (x < 0 || x >= n) return -1;
+    const int x = ed[2 * e], y = ed[2 * e + 1];
+    if (x < 0 || x >= n || y < 0 || y >= n) return -1;
     ++rp[x + 1];
   }
   for (long long i = 0; i < n; ++i) rp[i + 1] += rp[i];
@@ -273,24 +293,21 @@ int spmm_host_load_graph(const char* filename, int** rowptr, int** colind, int* 
   parallel_for(n, [&](int64_t lo, int64_t hi) {
     for (int64_t i = lo; i < hi; ++i) std::sort(ci.begin() + rp[i], ci.begin() + rp[i + 1]);
   });
-  int* rpo = static_cast<int*>(std::malloc(sizeof(int) * ((size_t)n + 1)));
-  int* cio = static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max(1LL, nnz)));
-  if (!rpo || !cio) {
-    std::free(rpo);
-    std::free(cio);
-    return -1;
-  }
-  std::memcpy(rpo, rp.data(), sizeof(int) * ((size_t)n + 1));
-  if (nnz) std::memcpy(cio, ci.data(), sizeof(int) * (size_t)nnz);
-  *rowptr = rpo;
-  *colind = cio;
+  Owned<int> rpo = owned_alloc<int>(n + 1), cio = owned_alloc<int>(nnz);
+  if (!rpo || !cio) return -1;
+  std::memcpy(rpo.get(), rp.data(), sizeof(int) * ((size_t)n + 1));
+  if (nnz) std::memcpy(cio.get(), ci.data(), sizeof(int) * (size_t)nnz);
+  *rowptr = rpo.release();
+  *colind = cio.release();
   *n_out = (int)n;
   *nnz_out = nnz;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_host_save_csr_bin(const char* path, int n, int64_t nnz, const int* rowptr,
-                           const int* colind, const float* val) {
+                           const int* colind, const float* val) try {
   if (!path || n < 0 || nnz < 0 || !rowptr || (nnz > 0 && !colind)) return -1;
   BinHeader h{};
   std::memcpy(h.magic, kMagic, 8);
@@ -316,53 +333,53 @@ int spmm_host_save_csr_bin(const char* path, int n, int64_t nnz, const int* rowp
     return -1;
   }
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_host_load_csr_bin(const char* path, int** rowptr, int** colind, float** val, int* n,
-                           int64_t* nnz) {
+                           int64_t* nnz) try {
   if (!path || !rowptr || !colind || !n || !nnz) return -1;
   FILE* f = std::fopen(path, "rb");
   if (!f) return -1;
+  struct Closer {
+    void operator()(FILE* x) const { std::fclose(x); }
+  };
+  const std::unique_ptr<FILE, Closer> close_f(f);
+  struct stat st;
   BinHeader h{};
-  if (std::fread(&h, sizeof h, 1, f) != 1 || std::memcmp(h.magic, kMagic, 8) != 0 ||
-      h.version != 1 || h.n < 0 || h.n > INT32_MAX || h.nnz < 0) {
-    std::fclose(f);
+  if (fstat(fileno(f), &st) != 0 || std::fread(&h, sizeof h, 1, f) != 1 ||
+      std::memcmp(h.magic, kMagic, 8) != 0 || h.version != 1 || h.n < 0 || h.n > INT32_MAX ||
+      h.nnz < 0 || h.nnz > INT32_MAX)
     return -1;
-  }
-  int* rp = static_cast<int*>(std::malloc(sizeof(int) * ((size_t)h.n + 1)));
-  int* ci = static_cast<int*>(std::malloc(sizeof(int) * (size_t)std::max<int64_t>(1, h.nnz)));
-  float* v = (h.flags & 1) ? static_cast<float*>(std::malloc(
-                                 sizeof(float) * (size_t)std::max<int64_t>(1, h.nnz)))
-                           : nullptr;
-  bool ok = rp && ci && (!(h.flags & 1) || v);
-  ok = ok && std::fread(rp, sizeof(int), (size_t)h.n + 1, f) == (size_t)h.n + 1;
-  ok = ok && (h.nnz == 0 || std::fread(ci, sizeof(int), (size_t)h.nnz, f) == (size_t)h.nnz);
-  ok = ok && (!v || h.nnz == 0 || std::fread(v, sizeof(float), (size_t)h.nnz, f) == (size_t)h.nnz);
-  std::fclose(f);
-  int rc = ok ? 0 : -1;
-  if (ok && (checksum(rp, sizeof(int) * ((size_t)h.n + 1), 1) != h.sum_rowptr ||
-             checksum(ci, sizeof(int) * (size_t)h.nnz, 2) != h.sum_colind ||
-             (v && checksum(v, sizeof(float) * (size_t)h.nnz, 3) != h.sum_val)))
-    rc = -2;
-  if (rc != 0 || (!val && v)) {
-    if (rc != 0) {
-      std::free(rp);
-      std::free(ci);
-    }
-    std::free(v);
-    v = nullptr;
-    if (rc != 0) return rc;
-  }
-  *rowptr = rp;
-  *colind = ci;
-  if (val) *val = v;
+  // The header's sizes against the file's, before anything is sized from them.
+  const bool has_val = (h.flags & 1) != 0;
+  const int64_t need = (int64_t)sizeof h + 4 * (h.n + 1) + (has_val ? 8 : 4) * h.nnz;
+  if ((int64_t)st.st_size < need) return -1;
+  Owned<int> rp = owned_alloc<int>(h.n + 1), ci = owned_alloc<int>(h.nnz);
+  Owned<float> v = has_val ? owned_alloc<float>(h.nnz) : Owned<float>();
+  if (!rp || !ci || (has_val && !v)) return -1;
+  if (std::fread(rp.get(), sizeof(int), (size_t)h.n + 1, f) != (size_t)h.n + 1 ||
+      (h.nnz > 0 && std::fread(ci.get(), sizeof(int), (size_t)h.nnz, f) != (size_t)h.nnz) ||
+      (v && h.nnz > 0 && std::fread(v.get(), sizeof(float), (size_t)h.nnz, f) != (size_t)h.nnz))
+    return -1;
+  if (checksum(rp.get(), sizeof(int) * ((size_t)h.n + 1), 1) != h.sum_rowptr ||
+      checksum(ci.get(), sizeof(int) * (size_t)h.nnz, 2) != h.sum_colind ||
+      (v && checksum(v.get(), sizeof(float) * (size_t)h.nnz, 3) != h.sum_val))
+    return -2;
+  if (!loaded_csr_ok(h.n, h.nnz, rp.get(), ci.get())) return -1;
+  *rowptr = rp.release();
+  *colind = ci.release();
+  if (val) *val = v.release();
   *n = (int)h.n;
   *nnz = h.nnz;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_host_load_csr_cached(const char* prefix, int** rowptr, int** colind, int* n,
-                              int64_t* nnz) {
+                              int64_t* nnz) try {
   if (!prefix) return -1;
   const std::string p(prefix), bin = p + ".csrbin";
   const int64_t t_bin = mtime_ns(bin);
@@ -373,6 +390,8 @@ int spmm_host_load_csr_cached(const char* prefix, int** rowptr, int** colind, in
   const int rc = spmm_host_load_csr(prefix, rowptr, colind, n, nnz);
   if (rc == 0) spmm_host_save_csr_bin(bin.c_str(), *n, *nnz, *rowptr, *colind, nullptr);
   return rc;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 }  // extern "C"

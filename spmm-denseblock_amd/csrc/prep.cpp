@@ -58,7 +58,7 @@ extern "C" {
 // with its own marker array), the prefix sums in between are sequential.
 spmm_status_t spmm_xcsr2bsr_nnz(spmm_direction_t dir, int m, int n, const int* csrRowPtr,
                                 const int* csrColInd, int blockDim, int* bsrRowPtr,
-                                int* nnzbTotal) {
+                                int* nnzbTotal) try {
   if (dir != SPMM_DIRECTION_ROW && dir != SPMM_DIRECTION_COLUMN) return SPMM_STATUS_INVALID_VALUE;
   if (m < 0 || n < 0 || blockDim <= 0) return SPMM_STATUS_INVALID_VALUE;
   if (!csrRowPtr || !bsrRowPtr || !nnzbTotal) return SPMM_STATUS_INVALID_VALUE;
@@ -84,11 +84,13 @@ spmm_status_t spmm_xcsr2bsr_nnz(spmm_direction_t dir, int m, int n, const int* c
   }
   *nnzbTotal = (int)acc;
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_scsr2bsr(spmm_direction_t dir, int m, int n, const float* csrVal,
                             const int* csrRowPtr, const int* csrColInd, int blockDim,
-                            const int* bsrRowPtr, float* bsrVal, int* bsrColInd) {
+                            const int* bsrRowPtr, float* bsrVal, int* bsrColInd) try {
   if (dir != SPMM_DIRECTION_ROW && dir != SPMM_DIRECTION_COLUMN) return SPMM_STATUS_INVALID_VALUE;
   if (m < 0 || n < 0 || blockDim <= 0) return SPMM_STATUS_INVALID_VALUE;
   if (!csrRowPtr || !bsrRowPtr) return SPMM_STATUS_INVALID_VALUE;
@@ -133,11 +135,13 @@ spmm_status_t spmm_scsr2bsr(spmm_direction_t dir, int m, int n, const float* csr
     }
   });
   return ok ? SPMM_STATUS_SUCCESS : SPMM_STATUS_INVALID_VALUE;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_sbsr2csr(spmm_direction_t dir, int mb, int nb, const float* bsrVal,
                             const int* bsrRowPtr, const int* bsrColInd, int blockDim,
-                            float* csrVal, int* csrRowPtr, int* csrColInd) {
+                            float* csrVal, int* csrRowPtr, int* csrColInd) try {
   if (dir != SPMM_DIRECTION_ROW && dir != SPMM_DIRECTION_COLUMN) return SPMM_STATUS_INVALID_VALUE;
   if (mb < 0 || nb < 0 || blockDim <= 0) return SPMM_STATUS_INVALID_VALUE;
   if (!bsrRowPtr || !csrRowPtr) return SPMM_STATUS_INVALID_VALUE;
@@ -167,14 +171,17 @@ spmm_status_t spmm_sbsr2csr(spmm_direction_t dir, int mb, int nb, const float* b
   }
   (void)nb;
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
-int64_t spmm_calculate_nnzb(int n, const int* csrRowPtr, const int* csrColInd, int blockDim) {
+int64_t spmm_calculate_nnzb(int n, const int* csrRowPtr, const int* csrColInd, int blockDim) try {
   if (n < 0 || blockDim <= 0 || !csrRowPtr) return -1;
   const int mb = ceil_div(n, blockDim);
   const int base = n > 0 ? csrRowPtr[0] : 0;
   int maxc = 0;
-  for (int j = 0; j < csrRowPtr[n] - base; ++j) maxc = std::max(maxc, csrColInd[j] - base);
+  // (n == 0: no entries whatever csrRowPtr[0] is, a base-1 pointer included)
+  for (int j = 0; n > 0 && j < csrRowPtr[n] - base; ++j) maxc = std::max(maxc, csrColInd[j] - base);
   const int nb = std::max(ceil_div(n, blockDim), maxc / blockDim + 1);
   std::vector<int> mark(std::max(nb, 1), -1), cols;
   int64_t total = 0;
@@ -183,9 +190,11 @@ int64_t spmm_calculate_nnzb(int n, const int* csrRowPtr, const int* csrColInd, i
     total += (int64_t)cols.size();
   }
   return total;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-spmm_status_t spmm_csr_partition_rows(int m, const int* csrRowPtr, int nparts, int* bounds) {
+spmm_status_t spmm_csr_partition_rows(int m, const int* csrRowPtr, int nparts, int* bounds) try {
   if (m < 0 || nparts <= 0 || !csrRowPtr || !bounds) return SPMM_STATUS_INVALID_VALUE;
   // Cost of the prefix [0, i) = nnz before row i + i (one unit per row for
   // its output write), monotone in i: cut at equal cost quantiles.
@@ -204,6 +213,8 @@ spmm_status_t spmm_csr_partition_rows(int m, const int* csrRowPtr, int nparts, i
   }
   bounds[nparts] = m;
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 // CSR -> CSC: the stable counting sort of the CSR positions by column (no reference
@@ -215,7 +226,7 @@ spmm_status_t spmm_csr_partition_rows(int m, const int* csrRowPtr, int nparts, i
 spmm_status_t spmm_csr2csc(int m, int n, int nnz, const void* csrVal, const int* csrRowPtr,
                            const int* csrColInd, int valueBytes, spmm_index_base_t baseA,
                            spmm_index_base_t baseC, void* cscVal, int* cscColPtr,
-                           int* cscRowInd, int* perm) {
+                           int* cscRowInd, int* perm) try {
   if (m < 0 || n < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
   if (valueBytes != 0 && valueBytes != 2 && valueBytes != 4 && valueBytes != 8)
     return SPMM_STATUS_INVALID_VALUE;
@@ -276,15 +287,12 @@ spmm_status_t spmm_csr2csc(int m, int n, int nnz, const void* csrVal, const int*
                       static_cast<const char*>(csrVal) + (size_t)p * valueBytes, valueBytes);
       }
   };
-  if (nt <= 1) {
-    fill(0, n);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-      if (cut[t] < cut[t + 1]) th.emplace_back(fill, cut[t], cut[t + 1]);
-    for (auto& x : th) x.join();
-  }
+  spmm_host::run_workers(nt, [&](int t) {
+    if (cut[t] < cut[t + 1]) fill(cut[t], cut[t + 1]);
+  });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 }  // extern "C"
@@ -326,7 +334,7 @@ extern "C" {
 spmm_status_t spmm_sddmm_csr_host_f32(int m, int n, int k, int nnz, float alpha,
                                       const int* csrRowPtr, const int* csrColInd,
                                       spmm_index_base_t base, const float* X, int ldx,
-                                      const float* Y, int ldy, float beta, float* outVal) {
+                                      const float* Y, int ldy, float beta, float* outVal) try {
   if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
   if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
     return SPMM_STATUS_INVALID_VALUE;
@@ -359,6 +367,8 @@ spmm_status_t spmm_sddmm_csr_host_f32(int m, int n, int k, int nnz, float alpha,
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 }  // extern "C"
@@ -422,7 +432,7 @@ extern "C" {
 // may be g: a row's inputs are read completely before its first output is written, except
 // the position's own.
 spmm_status_t spmm_edge_softmax_csr_host_f32(int m, int nnz, const int* csrRowPtr,
-                                             spmm_index_base_t base, const float* x, float* y) {
+                                             spmm_index_base_t base, const float* x, float* y) try {
   bool done;
   const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !x || !y, &done);
   if (done) return st;
@@ -440,11 +450,13 @@ spmm_status_t spmm_edge_softmax_csr_host_f32(int m, int nnz, const int* csrRowPt
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrRowPtr,
                                                  spmm_index_base_t base, const float* y,
-                                                 const float* g, float* gx) {
+                                                 const float* g, float* gx) try {
   bool done;
   const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !y || !g || !gx, &done);
   if (done) return st;
@@ -464,6 +476,8 @@ spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrR
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 // The three ops over `heads` heads (include/spmm_hip.h): per-edge values
@@ -472,7 +486,8 @@ spmm_status_t spmm_edge_softmax_bwd_csr_host_f32(int m, int nnz, const int* csrR
 spmm_status_t spmm_sddmm_csr_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
                                             const int* csrRowPtr, const int* csrColInd,
                                             spmm_index_base_t base, const float* X, int ldx,
-                                            const float* Y, int ldy, float beta, float* outVal) {
+                                            const float* Y, int ldy, float beta,
+                                            float* outVal) try {
   if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
   if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
     return SPMM_STATUS_INVALID_VALUE;
@@ -510,11 +525,13 @@ spmm_status_t spmm_sddmm_csr_heads_host_f32(int m, int d, int k, int nnz, int he
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_edge_softmax_csr_heads_host_f32(int m, int nnz, int heads,
                                                    const int* csrRowPtr, spmm_index_base_t base,
-                                                   const float* x, float* y) {
+                                                   const float* x, float* y) try {
   if (heads < 1) return SPMM_STATUS_INVALID_VALUE;
   bool done;
   const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !x || !y, &done);
@@ -537,12 +554,14 @@ spmm_status_t spmm_edge_softmax_csr_heads_host_f32(int m, int nnz, int heads,
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_edge_softmax_bwd_csr_heads_host_f32(int m, int nnz, int heads,
                                                        const int* csrRowPtr,
                                                        spmm_index_base_t base, const float* y,
-                                                       const float* g, float* gx) {
+                                                       const float* g, float* gx) try {
   if (heads < 1) return SPMM_STATUS_INVALID_VALUE;
   bool done;
   const spmm_status_t st = softmax_host_check(m, nnz, csrRowPtr, base, !y || !g || !gx, &done);
@@ -566,6 +585,8 @@ spmm_status_t spmm_edge_softmax_bwd_csr_heads_host_f32(int m, int nnz, int heads
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 // The product's piece rule on the host: a row of L nonzeros is cut into
@@ -574,7 +595,8 @@ spmm_status_t spmm_edge_softmax_bwd_csr_heads_host_f32(int m, int nnz, int heads
 spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads, float alpha,
                                         const int* csrRowPtr, const int* csrColInd,
                                         const float* csrVal, spmm_index_base_t base,
-                                        const float* B, int ldb, float beta, float* C, int ldc) {
+                                        const float* B, int ldb, float beta, float* C,
+                                        int ldc) try {
   if (m < 0 || d < 0 || k < 0 || nnz < 0 || heads < 1) return SPMM_STATUS_INVALID_VALUE;
   if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
     return SPMM_STATUS_INVALID_VALUE;
@@ -617,6 +639,8 @@ spmm_status_t spmm_csrmm_heads_host_f32(int m, int d, int k, int nnz, int heads,
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 // The max / min reducers of the CSR product and their backward on the host:
@@ -631,7 +655,7 @@ spmm_status_t spmm_csrmm_reduce_host_f32(spmm_reduce_t op, int m, int n, int k, 
                                          const int* csrRowPtr, const int* csrColInd,
                                          const float* csrVal, spmm_index_base_t base,
                                          const float* B, int ldb, float* C, int ldc, int* arg,
-                                         int ldarg) {
+                                         int ldarg) try {
   if (m < 0 || n < 0 || k < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
   if (op != SPMM_REDUCE_MAX && op != SPMM_REDUCE_MIN) return SPMM_STATUS_INVALID_VALUE;
   if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
@@ -683,6 +707,8 @@ spmm_status_t spmm_csrmm_reduce_host_f32(spmm_reduce_t op, int m, int n, int k, 
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 // Backward: row c of A^T, positions [ta, tb), column j: the selected positions
@@ -694,7 +720,7 @@ spmm_status_t spmm_csrmm_reduce_bwd_host_f32(int k, int n, int m, int nnz, const
                                              const int* tColInd, const int* perm,
                                              const float* csrVal, spmm_index_base_t base,
                                              const float* dC, int lddc, const int* arg,
-                                             int ldarg, float* dB, int lddb) {
+                                             int ldarg, float* dB, int lddb) try {
   if (k < 0 || n < 0 || m < 0 || nnz < 0) return SPMM_STATUS_INVALID_VALUE;
   if (base != SPMM_INDEX_BASE_ZERO && base != SPMM_INDEX_BASE_ONE)
     return SPMM_STATUS_INVALID_VALUE;
@@ -736,6 +762,8 @@ spmm_status_t spmm_csrmm_reduce_bwd_host_f32(int k, int n, int m, int nnz, const
     }
   });
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 }  // extern "C"
@@ -830,36 +858,45 @@ extern "C" {
 spmm_status_t spmm_sddmm_csr_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
                                             const int* csrRowPtr, const int* csrColInd,
                                             spmm_index_base_t base, const uint16_t* X, int ldx,
-                                            const uint16_t* Y, int ldy, float beta, float* outVal) {
+                                            const uint16_t* Y, int ldy, float beta,
+                                            float* outVal) try {
   return sddmm_heads_host_half(false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
                                ldx, Y, ldy, beta, outVal);
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_sddmm_csr_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
                                              const int* csrRowPtr, const int* csrColInd,
                                              spmm_index_base_t base, const uint16_t* X, int ldx,
                                              const uint16_t* Y, int ldy, float beta,
-                                             float* outVal) {
+                                             float* outVal) try {
   return sddmm_heads_host_half(true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, base, X,
                                ldx, Y, ldy, beta, outVal);
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_csrmm_heads_host_f16(int m, int d, int k, int nnz, int heads, float alpha,
                                         const int* csrRowPtr, const int* csrColInd,
                                         const float* csrVal, spmm_index_base_t base,
                                         const uint16_t* B, int ldb, float beta, float* C,
-                                        int ldc) {
+                                        int ldc) try {
   return csrmm_heads_host_half(false, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
                                base, B, ldb, beta, C, ldc);
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_csrmm_heads_host_bf16(int m, int d, int k, int nnz, int heads, float alpha,
                                          const int* csrRowPtr, const int* csrColInd,
                                          const float* csrVal, spmm_index_base_t base,
                                          const uint16_t* B, int ldb, float beta, float* C,
-                                         int ldc) {
+                                         int ldc) try {
   return csrmm_heads_host_half(true, m, d, k, nnz, heads, alpha, csrRowPtr, csrColInd, csrVal,
                                base, B, ldb, beta, C, ldc);
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 }  // extern "C"
@@ -912,7 +949,7 @@ extern "C" {
 
 spmm_status_t spmm_divide_nnz(int n, const int* rowPtr, const int* colInd, int blockDim,
                               float density, int* csrRowPtr, int* bsrRowPtr, int* csrNnz,
-                              int* nnzb) {
+                              int* nnzb) try {
   if (n < 0 || blockDim <= 0) return SPMM_STATUS_INVALID_VALUE;
   if (!rowPtr || !csrRowPtr || !bsrRowPtr || !csrNnz || !nnzb) return SPMM_STATUS_INVALID_VALUE;
   const int bs = blockDim, nb = ceil_div(n, bs), mb = nb;
@@ -959,12 +996,14 @@ spmm_status_t spmm_divide_nnz(int n, const int* rowPtr, const int* colInd, int b
   *csrNnz = (int)c_acc;
   *nnzb = (int)nb_acc;
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_sdivide(int n, const int* rowPtr, const int* colInd, const float* val,
                            int blockDim, float density, const int* csrRowPtr,
                            const int* bsrRowPtr, int* csrColInd, float* csrVal, int* bsrColInd,
-                           float* bsrVal) {
+                           float* bsrVal) try {
   if (n < 0 || blockDim <= 0) return SPMM_STATUS_INVALID_VALUE;
   if (!rowPtr || !csrRowPtr || !bsrRowPtr) return SPMM_STATUS_INVALID_VALUE;
   const int bs = blockDim, nb = ceil_div(n, bs), mb = nb;
@@ -1014,12 +1053,14 @@ spmm_status_t spmm_sdivide(int n, const int* rowPtr, const int* colInd, const fl
     }
   });
   return ok ? SPMM_STATUS_SUCCESS : SPMM_STATUS_INVALID_VALUE;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 spmm_status_t spmm_hybrid_plan(int n, const int* rowPtr, const int* colInd, int blockDim, int K,
                                int valueBytes, double bsrBytesPerSec, double csrBytesPerSec,
                                float* density, int64_t* nnzb, int64_t* csrNnz,
-                               double* estSeconds) {
+                               double* estSeconds) try {
   if (n < 0 || blockDim <= 0 || K <= 0 || valueBytes <= 0 || !rowPtr || !density)
     return SPMM_STATUS_INVALID_VALUE;
   const int bs = blockDim, nb = ceil_div(n, bs);
@@ -1033,31 +1074,28 @@ spmm_status_t spmm_hybrid_plan(int n, const int* rowPtr, const int* colInd, int 
   const int nt = spmm_host::num_threads();
   std::vector<std::vector<int64_t>> hist(nt, std::vector<int64_t>(bs2 + 1, 0));
   std::atomic<bool> ok{true};
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&, t] {
-      DivideScratch s(nb);
-      auto& h = hist[t];
-      for (int br = (int)((int64_t)nb * t / nt); br < (int)((int64_t)nb * (t + 1) / nt); ++br) {
-        s.touched.clear();
-        const int r0 = br * bs, r1 = std::min(n, r0 + bs);
-        for (int r = r0; r < r1; ++r)
-          for (int j = rowPtr[r] - base; j < rowPtr[r + 1] - base; ++j) {
-            const int c = colInd[j] - base;
-            if (c < 0 || c / bs >= nb) {
-              ok = false;
-              for (int x : s.touched) s.cnt[x] = 0;
-              return;
-            }
-            if (s.cnt[c / bs]++ == 0) s.touched.push_back(c / bs);
+  spmm_host::run_workers(nt, [&](int t) {
+    DivideScratch s(nb);
+    auto& h = hist[t];
+    for (int br = (int)((int64_t)nb * t / nt); br < (int)((int64_t)nb * (t + 1) / nt); ++br) {
+      s.touched.clear();
+      const int r0 = br * bs, r1 = std::min(n, r0 + bs);
+      for (int r = r0; r < r1; ++r)
+        for (int j = rowPtr[r] - base; j < rowPtr[r + 1] - base; ++j) {
+          const int c = colInd[j] - base;
+          if (c < 0 || c / bs >= nb) {
+            ok = false;
+            for (int x : s.touched) s.cnt[x] = 0;
+            return;
           }
-        for (int x : s.touched) {
-          ++h[std::min<int64_t>(s.cnt[x], bs2)];
-          s.cnt[x] = 0;
+          if (s.cnt[c / bs]++ == 0) s.touched.push_back(c / bs);
         }
+      for (int x : s.touched) {
+        ++h[std::min<int64_t>(s.cnt[x], bs2)];
+        s.cnt[x] = 0;
       }
-    });
-  for (auto& x : th) x.join();
+    }
+  });
   if (!ok) return SPMM_STATUS_INVALID_VALUE;
   for (int t = 1; t < nt; ++t)
     for (int64_t c = 0; c <= bs2; ++c) hist[0][c] += hist[t][c];
@@ -1086,6 +1124,8 @@ spmm_status_t spmm_hybrid_plan(int n, const int* rowPtr, const int* colInd, int 
   if (csrNnz) *csrNnz = best_rem;
   if (estSeconds) *estSeconds = best;
   return SPMM_STATUS_SUCCESS;
+} catch (...) {  // no exception leaves the C ABI
+  return SPMM_STATUS_ALLOC_FAILED;
 }
 
 }  // extern "C"

@@ -20,22 +20,10 @@ using spmm_host::parallel_for;
 
 namespace {
 
+// The graphs here are square: columns in [0, n) (host_util.hpp's check, shared with the
+// loaders of host_io.cpp).
 bool valid_csr(int n, const int* rowptr, const int* colind) {
-  if (n < 0 || (n > 0 && !rowptr)) return false;
-  if (n == 0) return true;
-  if (rowptr[0] != 0) return false;
-  for (int i = 0; i < n; ++i)
-    if (rowptr[i + 1] < rowptr[i]) return false;
-  if (rowptr[n] > 0 && !colind) return false;
-  std::atomic<bool> ok{true};
-  parallel_for(rowptr[n], [&](int64_t lo, int64_t hi) {
-    for (int64_t j = lo; j < hi; ++j)
-      if (colind[j] < 0 || colind[j] >= n) {
-        ok = false;
-        return;
-      }
-  });
-  return ok.load();
+  return spmm_host::valid_csr(n, rowptr, colind, n);
 }
 
 // BFS visit order (BFSTraversal, reorder_strategy.cc:84-114) over the
@@ -69,7 +57,7 @@ void bfs_order(int n, const int* rowptr, const int* adj, int* old2new) {
 
 extern "C" {
 
-int spmm_check_permutation(int n, const int* old2new) {
+int spmm_check_permutation(int n, const int* old2new) try {
   if (n < 0 || (n > 0 && !old2new)) return -1;
   std::vector<char> seen(n, 0);
   for (int i = 0; i < n; ++i) {
@@ -78,9 +66,11 @@ int spmm_check_permutation(int n, const int* old2new) {
     seen[v] = 1;
   }
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_reorder_degree(int n, const int* rowptr, const int* colind, int* old2new) {
+int spmm_reorder_degree(int n, const int* rowptr, const int* colind, int* old2new) try {
   if (!valid_csr(n, rowptr, colind) || (n > 0 && !old2new)) return -1;
   struct Node {
     int id, val;
@@ -92,15 +82,19 @@ int spmm_reorder_degree(int n, const int* rowptr, const int* colind, int* old2ne
   std::sort(nodes.begin(), nodes.end(), [](const Node& a, const Node& b) { return a.val > b.val; });
   for (int i = 0; i < n; ++i) old2new[nodes[i].id] = i;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_reorder_bfs(int n, const int* rowptr, const int* colind, int* old2new) {
+int spmm_reorder_bfs(int n, const int* rowptr, const int* colind, int* old2new) try {
   if (!valid_csr(n, rowptr, colind) || (n > 0 && !old2new)) return -1;
   bfs_order(n, rowptr, colind, old2new);
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_reorder_rcm(int n, const int* rowptr, const int* colind, int* old2new) {
+int spmm_reorder_rcm(int n, const int* rowptr, const int* colind, int* old2new) try {
   if (!valid_csr(n, rowptr, colind) || (n > 0 && !old2new)) return -1;
   const int64_t nnz = n ? rowptr[n] : 0;
   std::vector<int> adj(colind, colind + nnz);
@@ -114,10 +108,12 @@ int spmm_reorder_rcm(int n, const int* rowptr, const int* colind, int* old2new) 
   });
   bfs_order(n, rowptr, adj.data(), old2new);
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_permute_csr(int n, const int* rowptr, const int* colind, const float* val,
-                     const int* old2new, int* new_rowptr, int* new_colind, float* new_val) {
+                     const int* old2new, int* new_rowptr, int* new_colind, float* new_val) try {
   if (!valid_csr(n, rowptr, colind) || !new_rowptr || (!val) != (!new_val)) return -1;
   if (spmm_check_permutation(n, old2new) != 0) return -1;
   const int64_t nnz = n ? rowptr[n] : 0;
@@ -148,9 +144,11 @@ int spmm_permute_csr(int n, const int* rowptr, const int* colind, const float* v
     }
   });
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_load_permutation(const char* filename, int n, int* old2new) {
+int spmm_load_permutation(const char* filename, int n, int* old2new) try {
   if (!filename || n < 0 || (n > 0 && !old2new)) return -1;
   FILE* f = std::fopen(filename, "r");
   if (!f) return -1;
@@ -160,18 +158,22 @@ int spmm_load_permutation(const char* filename, int n, int* old2new) {
   std::fclose(f);
   if (i != n) return -1;
   return spmm_check_permutation(n, old2new);
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_dump_permutation(const char* filename, int n, const int* old2new) {
+int spmm_dump_permutation(const char* filename, int n, const int* old2new) try {
   if (!filename || spmm_check_permutation(n, old2new) != 0) return -1;
   FILE* f = std::fopen(filename, "w");
   if (!f) return -1;
   for (int i = 0; i < n; ++i) std::fprintf(f, "%d\n", old2new[i]);
   return std::fclose(f) == 0 ? 0 : -1;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 int spmm_block_metrics(int n, const int* rowptr, const int* colind, int blockDim,
-                       spmm_block_metrics_t* out) {
+                       spmm_block_metrics_t* out) try {
   if (!valid_csr(n, rowptr, colind) || blockDim <= 0 || !out) return -1;
   const int nb = (n + blockDim - 1) / blockDim;
   const int64_t nnz = n ? rowptr[n] : 0;
@@ -200,9 +202,12 @@ int spmm_block_metrics(int n, const int* rowptr, const int* colind, int blockDim
   out->utilization = nnzb ? (double)nnz / ((double)nnzb * bs * bs) : 0.0;
   out->average = nnzb ? (double)nnz / (double)nnzb : 0.0;
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_block_heatmap(int n, const int* rowptr, const int* colind, int blockDim, int* heatmap) {
+int spmm_block_heatmap(int n, const int* rowptr, const int* colind, int blockDim,
+                       int* heatmap) try {
   if (!valid_csr(n, rowptr, colind) || blockDim <= 0) return -1;
   const int64_t nb = (n + blockDim - 1) / blockDim;
   if (nb > 0 && !heatmap) return -1;
@@ -216,9 +221,11 @@ int spmm_block_heatmap(int n, const int* rowptr, const int* colind, int blockDim
     }
   });
   return 0;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
-int spmm_dump_heatmap(const char* filename, int nb, const int* heatmap) {
+int spmm_dump_heatmap(const char* filename, int nb, const int* heatmap) try {
   if (!filename || nb <= 0 || !heatmap) return -1;
   std::ofstream fs(filename);
   if (!fs) return -1;
@@ -235,6 +242,8 @@ int spmm_dump_heatmap(const char* filename, int nb, const int* heatmap) {
     fs << line;
   }
   return fs.good() ? 0 : -1;
+} catch (...) {  // no exception leaves the C ABI
+  return -1;
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import resource
 import time
 
 import numpy as np
@@ -85,6 +86,74 @@ def test_malformed_text_is_rejected(tmp_path):
     g.write_text("3 2\n0 1\n5 0\n")  # source out of range
     with pytest.raises(OSError):
         prep.load_graph(str(g))
+    # The loaders' contract (include/spmm_host.h): what they return is a CSR matrix. The
+    # arrays go on to device kernels that by contract do not validate.
+    graphs = {
+        "empty file": "",
+        "one token": "3\n",
+        "non-numeric token": "3 2\n0 1\n1 y\n",
+        "token past int range": "3 2\n0 1\n1 4294967297\n",
+        "fewer tokens than the header says": "3 3\n0 1\n1 2\n",
+        "destination out of range": "3 2\n0 1\n1 7\n",
+        "negative destination": "3 1\n0 -4\n",
+        "negative source": "3 1\n-1 0\n",
+        "negative n": "-3 1\n0 1\n",
+        "negative nnz": "3 -1\n0 1\n",
+    }
+    for what, text in graphs.items():
+        g.write_text(text)
+        with pytest.raises(OSError):
+            prep.load_graph(str(g))
+            pytest.fail(f"load_graph accepted: {what}")
+    # a header nnz of 2e9 over two edges: refused from the file's size, before the 16 GB of
+    # edge and column arrays it asks for are sized
+    g.write_text("3 2000000000\n0 1\n1 2\n")
+    before, t0 = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss, time.perf_counter()
+    with pytest.raises(OSError):
+        prep.load_graph(str(g))
+    assert time.perf_counter() - t0 < 1.0
+    assert resource.getrusage(resource.RUSAGE_SELF).ru_maxrss - before < 64 * 1024  # KiB
+    csrs = {
+        "empty files": ("", ""),
+        "one token": ("3\n", "1\n"),
+        "token past int range": ("3\n0 1 1\n", "1\n4294967297\n"),
+        "one column short": ("3\n0 1 2\n", "2\n0\n"),
+        "decreasing row pointer": ("3\n0 5 1\n", "1\n9\n"),
+        "row pointer not from 0": ("3\n1 1 2\n", "2\n0 1\n"),
+        "last row pointer is not nnz": ("3\n0 1 1\n", "2\n0 1\n"),
+        "negative column": ("3\n0 1 2\n", "2\n0 -1\n"),
+        "indptr count of 0": ("0\n", "0\n"),
+        "negative nnz": ("2\n0 0\n", "-1\n"),
+        "nnz of 2e9 over one column": ("2\n0 1\n", "2000000000\n0\n"),
+    }
+    for what, (indptr, indices) in csrs.items():
+        (tmp_path / "bad_indptr.txt").write_text(indptr)
+        (tmp_path / "bad_indices.txt").write_text(indices)
+        for load in (prep.load_csr, prep.load_csr_cached):
+            with pytest.raises(OSError):
+                load(str(p))
+                pytest.fail(f"{load.__name__} accepted: {what}")
+        assert not os.path.exists(str(p) + ".csrbin"), what  # nothing refused is cached
+    # the binary cache: truncated inside each array, sizes far past the file, and arrays that
+    # are intact by their checksums and still no CSR
+    rp, ci = np.array([0, 2, 2, 5], np.int32), np.array([1, 3, 0, 2, 4], np.int32)
+    f = str(tmp_path / "t.csrbin")
+    prep.save_csr_bin(f, rp, ci, np.arange(5, dtype=np.float32))
+    good = open(f, "rb").read()
+    assert len(good) == 56 + 16 + 20 + 20
+    for cut in (56 + 6, 56 + 16 + 9, 56 + 16 + 20 + 7):
+        open(f, "wb").write(good[:cut])
+        with pytest.raises(OSError):
+            prep.load_csr_bin(f)
+    for offset in (16, 24):  # n, nnz
+        open(f, "wb").write(good[:offset] + (1 << 30).to_bytes(8, "little") + good[offset + 8:])
+        with pytest.raises(OSError):
+            prep.load_csr_bin(f)
+    for bad_rp, bad_ci in (([0, 5, 1], [9]), ([0, 1, 2], [0, -1]), ([1, 1, 2], [0, 1]),
+                           ([0, 1, 2], [9])):
+        prep.save_csr_bin(f, np.array(bad_rp, np.int32), np.array(bad_ci, np.int32))
+        with pytest.raises(OSError):
+            prep.load_csr_bin(f)
 
 
 @pytest.mark.parametrize("with_val", [False, True])
