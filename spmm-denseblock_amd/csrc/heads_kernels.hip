@@ -27,21 +27,19 @@
 // No workspace, no atomics, no polling; every loop is bounded by m or nnz; positions are
 // clamped to [0, nnz] and rows to [0, m). The text of the sampled product and of the product
 // is heads_impl.hpp's, shared with the fp16 / bf16 forms (heads_half_kernels.hip) and
-// instantiated here for float; the helpers of the single-head files' anonymous namespaces
-// are restated there.
+// instantiated here for float; the body of a softmax row is softmax_impl.hpp's, shared with
+// the single-head kernel, and this file holds the loop over virtual rows around it. The
+// helpers of all of them (the walk, the folds, the launch) are csr_rows.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdint>
 
 #include "context.hpp"
 #include "heads_impl.hpp"
 #include "launch_record.hpp"
-#include "softmax_rule.hpp"
+#include "softmax_impl.hpp"
 
 namespace {
-
-using spmm_rule::softmax_exp;
 
 // ------------------------------------------------------------------ sampled product
 // (sddmm_heads_kernel<float, G, VEC>: heads_impl.hpp)
@@ -58,69 +56,7 @@ __global__ __launch_bounds__(kWG) void sddmm_heads_zero_kernel(int m, int nnz, i
 }
 
 // ------------------------------------------------------------------ edge softmax
-constexpr int kPiece = spmm_rule::kSoftmaxPiece;
-constexpr int kRound = 32;  // pieces whose sums meet in LDS at one barrier
-constexpr int kSoftmaxItemsPerWave = 2048;
-
-// One term of a chain at element e (= position * heads): the forward's EXP(x - mx) added,
-// the backward's fma(y, g, acc).
-template <bool BWD>
-__device__ __forceinline__ float chain(float acc, const float* u, const float* v, size_t e,
-                                       float mx) {
-  if constexpr (BWD) return __builtin_fmaf(u[e], v[e], acc);
-  else return acc + softmax_exp(u[e] - mx);
-}
-
-template <bool BWD>
-__device__ __forceinline__ float result(const float* u, const float* v, size_t e, float mx,
-                                        float s) {
-  if constexpr (BWD) {
-    const float diff = v[e] - s;
-    return u[e] * diff;
-  } else {
-    return softmax_exp(u[e] - mx) / s;
-  }
-}
-
-// One head of a row of L > kPiece positions by the whole workgroup (every thread calls it
-// with the same arguments); u, v, o point at the row's first element of that head, st is
-// the element stride. sums: kRound floats of LDS.
-template <bool BWD>
-__device__ void long_row(const float* u, const float* v, float* o, unsigned L, size_t st,
-                         float* sums) {
-  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1);
-  const unsigned wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-  float mx = -__builtin_inff();
-  if constexpr (!BWD) {
-    for (unsigned q = tid; q < L; q += kWG) mx = fmaxf(mx, u[q * st]);
-    mx = group_fold<kWave, true>(mx);
-    if (lane == 0) sums[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(sums[0], sums[1]), fmaxf(sums[2], sums[3]));
-    __syncthreads();
-  }
-  const unsigned npieces = (L + kPiece - 1) / kPiece;
-  float s = 0.f;
-  for (unsigned P0 = 0; P0 < npieces; P0 += kRound) {
-    const unsigned cnt = min((unsigned)kRound, npieces - P0);
-    for (unsigned P = wave; P < cnt; P += kWavesPerWG) {  // wave-uniform
-      const unsigned q0 = (P0 + P) * kPiece + lane;
-      float acc = 0.f;
-#pragma unroll 4
-      for (int i = 0; i < kPiece / kWave; ++i) {
-        const unsigned q = q0 + i * kWave;
-        if (q < L) acc = chain<BWD>(acc, u, v, q * st, mx);
-      }
-      acc = group_fold<kWave, false>(acc);
-      if (lane == 0) sums[P] = acc;
-    }
-    __syncthreads();
-    for (unsigned i = 0; i < cnt; ++i) s += sums[i];
-    __syncthreads();
-  }
-  for (unsigned q = tid; q < L; q += kWG) o[q * st] = result<BWD>(u, v, q * st, mx, s);
-}
-
+// (chain, result and long_row: softmax_impl.hpp, at element stride heads)
 // BWD false: u = x, v unused, o = y.  BWD true: u = y, v = g, o = gx. All [nnz, heads].
 template <int G, bool BWD>
 __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz, int heads,
@@ -134,7 +70,7 @@ __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz,
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sub = lane & (G - 1), grp = lane / G;
-  const size_t st = (size_t)heads;
+  const Strided at{(size_t)heads};
 
   const Rows wr = wave_rows(rowptr, m, base, nnz, wave);
   if (tid == 0) s_rows[0] = wr.r0;
@@ -149,13 +85,15 @@ __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz,
     const long long a = row_pos(rowptr, r, base, nnz);
     const long long len = row_pos(rowptr, r + 1, base, nnz) - a;
     const unsigned L = vb + grp < v1 && len > 0 && len <= kPiece ? (unsigned)len : 0u;
-    const size_t off = (size_t)a * st + h;
+    const size_t off = (size_t)a * at.heads + h;
     const float* ur = u + off;
     const float* vp = v + off;
     float* orow = o + off;
+    // (edge_softmax_kernel's lane-group body at stride heads: softmax_impl.hpp says why
+    // the two are not one function)
     float mx = -__builtin_inff();
     if constexpr (!BWD) {
-      for (unsigned q = sub; q < L; q += G) mx = fmaxf(mx, ur[q * st]);
+      for (unsigned q = sub; q < L; q += G) mx = fmaxf(mx, ur[at(q)]);
       mx = group_fold<G, true>(mx);
     }
     float acc[NB];
@@ -165,7 +103,7 @@ __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz,
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         const unsigned q = q0 + G * j + sub;
-        if (q < L) acc[j] = chain<BWD>(acc[j], ur, vp, q * st, mx);
+        if (q < L) acc[j] = chain<BWD>(acc[j], ur, vp, at(q), mx);
       }
     }
     // chains G j .. G j + G - 1 across the lanes, then the tree over j in registers
@@ -176,7 +114,7 @@ __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz,
 #pragma unroll
       for (int j = 0; j < wd / 2; ++j) acc[j] = acc[2 * j] + acc[2 * j + 1];
     const float s = acc[0];
-    for (unsigned q = sub; q < L; q += G) orow[q * st] = result<BWD>(ur, vp, q * st, mx, s);
+    for (unsigned q = sub; q < L; q += G) orow[at(q)] = result<BWD>(ur, vp, at(q), mx, s);
   }
 
   // long rows of the workgroup's range, each head by all four waves
@@ -184,8 +122,8 @@ __global__ __launch_bounds__(kWG) void edge_softmax_heads_kernel(int m, int nnz,
   for_long_rows(rowptr, m, base, nnz, s_rows[0], s_rows[1], kPiece, s_mask,
                 [&](int, long long a, long long b) {
                   for (int h = 0; h < heads; ++h) {
-                    const size_t off = (size_t)a * st + h;
-                    long_row<BWD>(u + off, v + off, o + off, (unsigned)(b - a), st, s_sums);
+                    const size_t off = (size_t)a * at.heads + h;
+                    long_row<BWD>(u + off, v + off, o + off, (unsigned)(b - a), at, s_sums);
                   }
                 });
 }
@@ -226,20 +164,13 @@ spmm_status_t launch_sddmm_heads(spmm_context* ctx, int m, int d, int nnz, int h
 spmm_status_t launch_edge_softmax_heads(spmm_context* ctx, bool bwd, int m, int nnz, int heads,
                                         const int* rowptr, int base, const float* u,
                                         const float* v, float* o) {
-  // lanes per short row from the mean row length, as in the single-head kernel
-  const long long mean = ((long long)nnz + m - 1) / m;
-  const int G = mean <= 8 ? 4 : mean <= 48 ? 16 : 64;
-  const Picked<SoftmaxKernel> kern = bwd ? pick_softmax<true>(G) : pick_softmax<false>(G);
+  const int G = softmax_group_lanes(m, nnz);
   // the share is the kernel's own, from the row pointer's count; a wave's items carry
   // heads elements each
   const unsigned grid = merge_grid(ctx, (long long)m + nnz,
                                    std::max<long long>(kSoftmaxItemsPerWave / heads, 64));
-  const int slot = timing_begin(ctx);
-  note_launch(ctx, kern.id);
-  hipLaunchKernelGGL(kern.fn, dim3(grid), dim3(kWG), 0, ctx->stream, m, nnz, heads, rowptr, base,
-                     u, v, o);
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return launch_picked(ctx, bwd ? pick_softmax<true>(G) : pick_softmax<false>(G), dim3(grid),
+                       dim3(kWG), m, nnz, heads, rowptr, base, u, v, o);
 }
 
 spmm_status_t launch_csrmm_heads(spmm_context* ctx, int m, int d, int nnz, int heads,

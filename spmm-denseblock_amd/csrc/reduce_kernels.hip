@@ -21,8 +21,9 @@
 // counted over all positions, so the text is csrmm_heads_kernel's with the select in the
 // chain. arg is compared and never used as an index.
 // No workspace, no atomics, no polling; every loop is bounded by the row count or nnz;
-// positions are clamped to [0, nnz] and rows to [0, m). The helpers (the merge-path share,
-// the long-row walk, the vector loads) are heads_impl.hpp's.
+// positions are clamped to [0, nnz] and rows to [0, m). The merge-path share, the long-row
+// walk and the grid are csr_rows.hpp's; the vector loads and stores of a lane's columns
+// (Cols) and the piece constants are heads_impl.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +31,7 @@
 #include <type_traits>
 
 #include "context.hpp"
+#include "csr_rows.hpp"
 #include "heads_impl.hpp"
 #include "launch_record.hpp"
 

@@ -23,119 +23,20 @@
 // share's last position, an empty chunk reads the row's last one), since a load inside a
 // branch is waited for inside it. Folds inside 16 lanes are DPP row rotations (the value
 // is complete in a group's last lane), across rows two shuffles. No workspace, no
-// atomics, no synchronisation.
+// atomics, no synchronisation. The fold, the share, the chunk loads and the launch are
+// csr_rows.hpp's, shared with the multi-head kernel (heads_impl.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdint>
 
 #include "context.hpp"
-#include "launch_record.hpp"
+#include "csr_rows.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWG = 256;
-constexpr int kWavesPerWG = kWG / kWave;
 // n up to 4 * 64 * kMaxChunks keeps the X slice in registers; wider rows take
 // sddmm_wide_kernel
 constexpr int kMaxChunks = 4;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// x from lane (l - N) mod 16 of the same 16-lane row (DPP row_ror:N).
-template <int N>
-__device__ __forceinline__ float dpp_ror(float x) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + N, 0xF, 0xF, false));
-}
-
-// The butterfly sum of the G chains of a lane group, complete in the group's last lane
-// (lane % G == G - 1): after the rotations by 1, 2, ..., s / 2 a lane whose low bits are
-// all ones holds (its half) + (the other half), each half summed the same way, which is
-// acc_l + acc_(l xor s) at every level. Every lane of the wave must be active.
-template <int G>
-__device__ __forceinline__ float fold(float x) {
-  if constexpr (G >= 2) x += dpp_ror<1>(x);
-  if constexpr (G >= 4) x += dpp_ror<2>(x);
-  if constexpr (G >= 8) x += dpp_ror<4>(x);
-  if constexpr (G >= 16) x += dpp_ror<8>(x);
-  if constexpr (G >= 32) x += __shfl_xor(x, 16);
-  if constexpr (G >= 64) x += __shfl_xor(x, 32);
-  return x;
-}
-
-// Columns c0 .. c0 + 3 of a row, without a branch, so that the loads of several steps
-// stay in flight together. VEC (16-byte bases, ld % 4 == 0 and n % 4 == 0: a chunk is
-// whole or empty): one dwordx4, an empty chunk reading the row's last one instead.
-// Otherwise one dword per column, a column from n on reading column n - 1 instead.
-// What is read in place of a missing column is never summed (chain4). n > 0.
-template <bool VEC, bool FULL>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ row, int c0, int n) {
-  if constexpr (VEC) {
-    return *reinterpret_cast<const f32x4*>(row + (FULL ? c0 : min(c0, n - 4)));
-  } else {
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[FULL ? c0 + e : min(c0 + e, n - 1)];
-    return v;
-  }
-}
-
-// FULL: n is a multiple of 4 G, so every lane's chunks are whole.
-template <bool FULL>
-__device__ __forceinline__ float chain4(float acc, const f32x4& x, const f32x4& y, int c0, int n) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (FULL || c0 + e < n) acc = __builtin_fmaf(x[e], y[e], acc);
-  return acc;
-}
-
-// Waits for a pending load into `x` right here (the rare reload path), so that the
-// common path that merges with it after the branch does not inherit a full wait.
-template <typename T>
-__device__ __forceinline__ void settle(T& x) {
-  asm volatile("" : "+v"(x));
-}
-
-// The positions of the pattern, clamped to what csrColInd / outVal hold (nnz is an int,
-// so a position fits 32 bits, and a position plus a few steps fits an unsigned: a share ends
-// at b <= INT_MAX and the last batch reaches at most PD * S + 63 < 2^10 positions past it;
-// every such sum in the kernels is an unsigned and is clamped to b - 1 as one; held at
-// rowptr[m] - base = INT_MAX by tests/test_gpu_far_positions.py), and wave w's share
-// [a, b): whole steps of S positions.
-struct Share {
-  unsigned a, b;
-};
-__device__ __forceinline__ Share wave_share(const int* __restrict__ rowptr, int m, int base,
-                                            int nnz, int S) {
-  const long long w = (long long)blockIdx.x * kWavesPerWG +
-                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long nwaves = (long long)gridDim.x * kWavesPerWG;
-  const long long p0 = max((long long)rowptr[0] - base, 0ll);
-  const long long p1 = min((long long)rowptr[m] - base, (long long)nnz);
-  if (p1 <= p0) return {0u, 0u};
-  const long long steps = (p1 - p0 + S - 1) / S;
-  const long long per = (steps + nwaves - 1) / nwaves;
-  const long long a = p0 + min(w * per, steps) * S;
-  return {(unsigned)min(a, p1), (unsigned)min(a + per * S, p1)};
-}
-
-// The row of position p (the last row that starts at or before it), in [0, m - 1].
-__device__ __forceinline__ int find_row(const int* __restrict__ rowptr, int m, int base,
-                                        long long p) {
-  int lo = 0, hi = m - 1;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if ((long long)rowptr[mid] - base <= p) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ float epilogue(float d, float alpha, float beta, const float* op) {
-  return beta == 0.f ? alpha * d : __builtin_fmaf(beta, *op, alpha * d);
-}
 
 template <int G, int NC, bool VEC, bool FULL>
 __global__ __launch_bounds__(kWG) void sddmm_kernel(int m, int n, int nnz,
@@ -185,7 +86,7 @@ __global__ __launch_bounds__(kWG) void sddmm_kernel(int m, int n, int nnz,
     for (int u = 0; u < PD; ++u) {
       const float* yp = Y + (long long)(j[u] - base) * ldy;
 #pragma unroll
-      for (int t = 0; t < NC; ++t) y[u][t] = load4<VEC, FULL>(yp, 4 * (sub + G * t), n);
+      for (int t = 0; t < NC; ++t) y[u][t] = load4<float, VEC, FULL>(yp, 4 * (sub + G * t), n);
     }
 #pragma unroll
     for (int u = 0; u < PD; ++u) {
@@ -195,7 +96,7 @@ __global__ __launch_bounds__(kWG) void sddmm_kernel(int m, int n, int nnz,
           const float* xp = X + (long long)rx * ldx;
 #pragma unroll
           for (int t = 0; t < NC; ++t) {
-            x[t] = load4<VEC, FULL>(xp, 4 * (sub + G * t), n);
+            x[t] = load4<float, VEC, FULL>(xp, 4 * (sub + G * t), n);
             settle(x[t]);
           }
         }
@@ -235,7 +136,8 @@ __global__ __launch_bounds__(kWG) void sddmm_wide_kernel(int m, int n, int nnz,
     const float* yp = Y + (long long)(colind[p] - base) * ldy;
     float acc = 0.f;
     for (int c0 = 4 * lane; c0 < n; c0 += 4 * kWave)
-      acc = chain4<false>(acc, load4<VEC, false>(xp, c0, n), load4<VEC, false>(yp, c0, n), c0, n);
+      acc = chain4<false>(acc, load4<float, VEC, false>(xp, c0, n),
+                          load4<float, VEC, false>(yp, c0, n), c0, n);
     const float d = fold<kWave>(acc);
     if (lane == kWave - 1) out[p] = epilogue(d, alpha, beta, out + p);
   }
@@ -252,27 +154,11 @@ __global__ __launch_bounds__(kWG) void sddmm_zero_kernel(int m, int nnz,
     out[p] = epilogue(0.f, alpha, beta, out + p);
 }
 
-inline int group_lanes(int n) {
-  const int chunks = (n + 3) / 4;
-  int g = 1;
-  while (g < chunks && g < kWave) g <<= 1;
-  return g;
-}
-
 using Kernel = void (*)(int, int, int, const int*, const int*, int, const float*, long long,
                         const float*, long long, float, float, float*);
-// a kernel chosen at run time, with its launch-record identifier (launch_record.hpp)
-struct Picked {
-  Kernel fn;
-  const char* id;
-};
-template <auto K>
-Picked picked() {
-  return {K, spmm::launch_id<K>()};
-}
 
 template <int G, int NC>
-Picked pick(bool vec, bool full) {
+Picked<Kernel> pick(bool vec, bool full) {
   if (vec) {
     // G = 1 / 2 (n <= 8): the only n with n % 4 == 0 is 4 G itself, so vec implies full
     if constexpr (G > 2)
@@ -290,11 +176,10 @@ namespace spmm {
 spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* rowptr,
                            const int* colind, int base, const float* X, int ldx, const float* Y,
                            int ldy, float alpha, float beta, float* out) {
-  const int G = group_lanes(n);
+  const int G = sddmm_group_lanes(n);
   const int chunks = (n + 3) / 4;
   const int NC = std::max(1, (chunks + G - 1) / G);
-  const bool vec = n % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
-                   reinterpret_cast<uintptr_t>(Y) % 16 == 0 && ldx % 4 == 0 && ldy % 4 == 0;
+  const bool vec = n % 4 == 0 && aligned(X, 16) && aligned(Y, 16) && ldx % 4 == 0 && ldy % 4 == 0;
   const bool full = n % (4 * G) == 0;
   if (n == 0) {
     const unsigned zgrid = (unsigned)std::min<long long>(((long long)nnz + kWG - 1) / kWG, 65536);
@@ -304,7 +189,7 @@ spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* 
     timing_end(ctx, zslot);
     return from_hip(hipGetLastError());
   }
-  Picked kern{};
+  Picked<Kernel> kern{};
   if (NC > kMaxChunks)
     kern = vec ? picked<sddmm_wide_kernel<true>>() : picked<sddmm_wide_kernel<false>>();
   else if (G == 1) kern = pick<1, 1>(vec, full);
@@ -324,12 +209,8 @@ spmm_status_t launch_sddmm(spmm_context* ctx, int m, int n, int nnz, const int* 
   const long long waves = std::min<long long>(std::max<long long>((steps + 31) / 32, 1),
                                               (long long)ctx->num_cus * 128);
   const unsigned grid = (unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG);
-  const int slot = timing_begin(ctx);
-  spmm::note_launch(ctx, kern.id);
-  hipLaunchKernelGGL(kern.fn, dim3(grid), dim3(kWG), 0, ctx->stream, m, n, nnz, rowptr, colind,
-                     base, X, (long long)ldx, Y, (long long)ldy, alpha, beta, out);
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  return launch_picked(ctx, kern, dim3(grid), dim3(kWG), m, n, nnz, rowptr, colind, base, X,
+                       (long long)ldx, Y, (long long)ldy, alpha, beta, out);
 }
 
 }  // namespace spmm

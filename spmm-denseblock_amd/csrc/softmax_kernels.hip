@@ -28,128 +28,15 @@
 // clamped to [0, nnz] and rows to [0, m), so that a bad row pointer reads nothing out of
 // bounds. y may be x and gx may be g: a position is read and written by one lane, and the
 // row's reads of the earlier passes are complete (fold or barrier) before its first store.
+// The row walk is csr_rows.hpp's; a chain's term, the output at a position and the long row
+// are softmax_impl.hpp's, shared with the multi-head kernel (heads_kernels.hip).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdint>
-
 #include "context.hpp"
-#include "launch_record.hpp"
-#include "softmax_rule.hpp"
+#include "csr_rows.hpp"
+#include "softmax_impl.hpp"
 
 namespace {
-
-using spmm_rule::softmax_exp;
-
-constexpr int kWave = 64;
-constexpr int kWG = 256;
-constexpr int kWavesPerWG = kWG / kWave;
-constexpr int kPiece = spmm_rule::kSoftmaxPiece;
-constexpr int kRound = 32;  // pieces whose sums meet in LDS at one barrier
-// merge-path items (rows + positions) a wave is given when the grid is not capped
-constexpr int kItemsPerWave = 2048;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
-}
-
-// x of lane (l xor S). Every lane of the wave must be active.
-template <int S>
-__device__ __forceinline__ float from_xor(float x) {
-  if constexpr (S == 1) return dpp<0xB1>(x);        // quad_perm:[1,0,3,2]
-  else if constexpr (S == 2) return dpp<0x4E>(x);   // quad_perm:[2,3,0,1]
-  else if constexpr (S == 8) return dpp<0x128>(x);  // row_ror:8, l - 8 mod 16 == l xor 8
-  else return __shfl_xor(x, S);
-}
-
-// The butterfly over the G lanes of a group, complete in every lane (addition and max
-// commute, so both sides of a pair hold the same bits).
-template <int G, bool MAX, int S = 1>
-__device__ __forceinline__ float group_fold(float x) {
-  if constexpr (S < G) {
-    const float o = from_xor<S>(x);
-    return group_fold<G, MAX, 2 * S>(MAX ? fmaxf(x, o) : x + o);
-  } else {
-    return x;
-  }
-}
-
-// Position rowptr[r] - base, clamped to what x / y hold.
-__device__ __forceinline__ long long row_pos(const int* __restrict__ rowptr, int r, int base,
-                                             int nnz) {
-  return min(max((long long)rowptr[r] - base, 0ll), (long long)nnz);
-}
-
-// The first row in [0, m] whose merge-path coordinate r + row_pos(r) reaches t.
-__device__ __forceinline__ int first_row(const int* __restrict__ rowptr, int m, int base, int nnz,
-                                         long long t) {
-  int lo = 0, hi = m;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (mid + row_pos(rowptr, mid, base, nnz) >= t) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
-// One term of a chain: the forward's e = EXP(x - mx) added, the backward's fma(y, g, acc).
-template <bool BWD>
-__device__ __forceinline__ float chain(float acc, const float* u, const float* v, unsigned q,
-                                       float mx) {
-  if constexpr (BWD) return __builtin_fmaf(u[q], v[q], acc);
-  else return acc + softmax_exp(u[q] - mx);
-}
-
-// The output at q from the row's s (the forward's sum, the backward's d).
-template <bool BWD>
-__device__ __forceinline__ float result(const float* u, const float* v, unsigned q, float mx,
-                                        float s) {
-  if constexpr (BWD) {
-    const float diff = v[q] - s;
-    return u[q] * diff;
-  } else {
-    return softmax_exp(u[q] - mx) / s;
-  }
-}
-
-// A row of L > kPiece positions by the whole workgroup (every thread calls it with the
-// same arguments). sums: kRound floats of LDS.
-template <bool BWD>
-__device__ void long_row(const float* u, const float* v, float* o, unsigned L, float* sums) {
-  const unsigned tid = threadIdx.x, lane = tid & (kWave - 1);
-  const unsigned wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-  float mx = -__builtin_inff();
-  if constexpr (!BWD) {
-    for (unsigned q = tid; q < L; q += kWG) mx = fmaxf(mx, u[q]);
-    mx = group_fold<kWave, true>(mx);
-    if (lane == 0) sums[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(sums[0], sums[1]), fmaxf(sums[2], sums[3]));
-    __syncthreads();
-  }
-  const unsigned npieces = (L + kPiece - 1) / kPiece;
-  float s = 0.f;
-  for (unsigned P0 = 0; P0 < npieces; P0 += kRound) {
-    const unsigned cnt = min((unsigned)kRound, npieces - P0);
-    for (unsigned P = wave; P < cnt; P += kWavesPerWG) {  // wave-uniform
-      const unsigned q0 = (P0 + P) * kPiece + lane;
-      float acc = 0.f;
-#pragma unroll 4
-      for (int i = 0; i < kPiece / kWave; ++i) {
-        const unsigned q = q0 + i * kWave;
-        if (q < L) acc = chain<BWD>(acc, u, v, q, mx);
-      }
-      acc = group_fold<kWave, false>(acc);
-      if (lane == 0) sums[P] = acc;
-    }
-    __syncthreads();
-    for (unsigned i = 0; i < cnt; ++i) s += sums[i];
-    __syncthreads();
-  }
-  for (unsigned q = tid; q < L; q += kWG) o[q] = result<BWD>(u, v, q, mx, s);
-}
 
 // BWD false: u = x, v unused, o = y.  BWD true: u = y, v = g, o = gx.
 template <int G, bool BWD>
@@ -165,23 +52,16 @@ __global__ __launch_bounds__(kWG) void edge_softmax_kernel(int m, int nnz,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sub = lane & (G - 1), grp = lane / G;
 
-  // the wave's rows [wr0, wr1): those whose merge-path coordinate lies in its share
-  const long long p0 = row_pos(rowptr, 0, base, nnz);
-  const long long items = (long long)m + max(row_pos(rowptr, m, base, nnz) - p0, 0ll);
-  const long long nwaves = (long long)gridDim.x * kWavesPerWG;
-  const long long per = (items + nwaves - 1) / nwaves;
-  const long long w = (long long)blockIdx.x * kWavesPerWG + wave;
-  const int wr0 = first_row(rowptr, m, base, nnz, p0 + min(w * per, items));
-  const int wr1 = first_row(rowptr, m, base, nnz, p0 + min((w + 1) * per, items));
-  if (tid == 0) s_rows[0] = wr0;
-  if (tid == kWG - 1) s_rows[1] = wr1;
+  const Rows wr = wave_rows(rowptr, m, base, nnz, wave);
+  if (tid == 0) s_rows[0] = wr.r0;
+  if (tid == kWG - 1) s_rows[1] = wr.r1;
 
-  // short rows
-  for (int rb = wr0; rb < wr1; rb += NB) {  // wave-uniform
+  // short rows: a lane group takes a row
+  for (int rb = wr.r0; rb < wr.r1; rb += NB) {  // wave-uniform
     const int r = min(rb + grp, m - 1);
     const long long a = row_pos(rowptr, r, base, nnz);
     const long long len = row_pos(rowptr, r + 1, base, nnz) - a;
-    const unsigned L = rb + grp < wr1 && len > 0 && len <= kPiece ? (unsigned)len : 0u;
+    const unsigned L = rb + grp < wr.r1 && len > 0 && len <= kPiece ? (unsigned)len : 0u;
     const float* ur = u + a;
     const float* vr = v + a;
     float* orow = o + a;
@@ -211,7 +91,10 @@ __global__ __launch_bounds__(kWG) void edge_softmax_kernel(int m, int nnz,
     for (unsigned q = sub; q < L; q += G) orow[q] = result<BWD>(ur, vr, q, mx, s);
   }
 
-  // long rows of the workgroup's range, each by all four waves
+  // long rows of the workgroup's range, each by all four waves: for_long_rows' walk
+  // (csr_rows.hpp), written out here, since through the function every instantiation grows
+  // by 11 instructions (it takes the wave index anew) and two of them measured slower
+  // (profiles/csr_rows/edge_softmax_for_long_rows/)
   __syncthreads();
   const int R0 = s_rows[0], R1 = s_rows[1];
   for (int rb = R0; rb < R1; rb += kWG) {  // workgroup-uniform
@@ -230,30 +113,16 @@ __global__ __launch_bounds__(kWG) void edge_softmax_kernel(int m, int nnz,
         bits &= bits - 1;
         const long long a = row_pos(rowptr, row, base, nnz);
         const long long b = row_pos(rowptr, row + 1, base, nnz);
-        long_row<BWD>(u + a, v + a, o + a, (unsigned)(b - a), s_sums);
+        long_row<BWD>(u + a, v + a, o + a, (unsigned)(b - a), Unit{}, s_sums);
       }
     }
     __syncthreads();
   }
 }
 
-// lanes per short row from the mean row length
-inline int group_lanes(int m, int nnz) {
-  const long long mean = ((long long)nnz + m - 1) / m;
-  return mean <= 8 ? 4 : mean <= 48 ? 16 : 64;
-}
-
 using Kernel = void (*)(int, int, const int*, int, const float*, const float*, float*);
-struct Picked {
-  Kernel fn;
-  const char* id;
-};
-template <auto K>
-Picked picked() {
-  return {K, spmm::launch_id<K>()};
-}
 template <bool BWD>
-Picked pick(int G) {
+Picked<Kernel> pick(int G) {
   if (G == 4) return picked<edge_softmax_kernel<4, BWD>>();
   if (G == 16) return picked<edge_softmax_kernel<16, BWD>>();
   return picked<edge_softmax_kernel<64, BWD>>();
@@ -265,24 +134,12 @@ namespace spmm {
 
 spmm_status_t launch_edge_softmax(spmm_context* ctx, bool bwd, int m, int nnz, const int* rowptr,
                                   int base, const float* u, const float* v, float* o) {
-  const Picked kern = bwd ? pick<true>(group_lanes(m, nnz)) : pick<false>(group_lanes(m, nnz));
+  const int G = softmax_group_lanes(m, nnz);
   // the share is computed in the kernel from the row pointer's own count; the grid's size
   // cannot reach the output (a row's bits are the row's)
-  const long long items = (long long)m + nnz;
-  // kItemsPerWave items per wave up to 32 waves per CU; spmm_set_csr_waves_per_cu sets
-  // the wave count itself (at least one item each)
-  const long long waves =
-      ctx->csr_waves_per_cu > 0
-          ? std::min<long long>((long long)ctx->num_cus * ctx->csr_waves_per_cu, items)
-          : std::min<long long>((items + kItemsPerWave - 1) / kItemsPerWave,
-                                (long long)ctx->num_cus * 32);
-  const unsigned grid = (unsigned)((waves + kWavesPerWG - 1) / kWavesPerWG);
-  const int slot = timing_begin(ctx);
-  spmm::note_launch(ctx, kern.id);
-  hipLaunchKernelGGL(kern.fn, dim3(grid), dim3(kWG), 0, ctx->stream, m, nnz, rowptr, base, u, v,
-                     o);
-  timing_end(ctx, slot);
-  return from_hip(hipGetLastError());
+  const unsigned grid = merge_grid(ctx, (long long)m + nnz, kSoftmaxItemsPerWave);
+  return launch_picked(ctx, bwd ? pick<true>(G) : pick<false>(G), dim3(grid), dim3(kWG), m, nnz,
+                       rowptr, base, u, v, o);
 }
 
 }  // namespace spmm
